@@ -19,16 +19,26 @@ that the headline instead.
 Rays = segments = closest-hit queries (primary + reflection), counted exactly by the
 kernel in an untimed census launch.
 
-Order of a run: census; side measurements (per-precision kernel sweep, sun-on frame loop,
-moving-camera frame loop, and `steady_state`: the timed loop itself over 200 frames —
-before the timed region, so it starts on a GPU at its running clock with the measured
-tile-row order settled, as inside a running frame loop); W warmup + K timed steps, each
-enqueued by one C-ABI call per region
-(rt_multi_render_device_frames / rt_render_device_frames: every frame's own host work and
-launch, as a C++ frame loop does them, without Python's per-call overhead); the one-stream
-kernel time; the frame-sharded side run (N > 1); the CPU baseline (rank 0, N = 1).
+A plain run does only what the headline needs: census; the conditioning loops (the timed
+loop itself over 200 frames, then a bounded number of windows like the timed region — so
+the timed region starts on a GPU at its running clock with the measured tile-row order
+settled, as inside a running frame loop); W warmup + K timed steps, each enqueued by one
+C-ABI call per region (rt_multi_render_device_frames / rt_render_device_frames: every
+frame's own host work and launch, as a C++ frame loop does them, without Python's per-call
+overhead); the JSON line.  `--dump-outputs DIR` also writes the last timed step's frame.
+
+`--full` adds everything else, in this order: the gather check (the gathered frames against
+the one-GPU frame, bitwise) before the side measurements (per-precision kernel sweep,
+sun-on frame loop, moving-camera frame loop); the conditioning loops reported as
+`steady_state` and `window_rhythm`; after the timed region the one-stream kernel time and
+the rooflines priced on it, the frame-sharded and RGBA8 side runs (N > 1), the config-5
+side run, the CPU baseline (rank 0, N = 1).  `--no-sweep`, `--no-c5` and
+`--no-cpu-baseline` trim a full run (`--full --no-sweep` also skips the conditioning loops,
+as `--no-sweep` did before there was `--full`); without `--full` they change nothing and the
+run says so on stderr.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--precision mixed]
+    python bench.py --full                               # every side measurement and check
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Process model: one process per GPU.  Under a launcher (torch.distributed.run: RANK /
@@ -136,6 +146,23 @@ def load_profile(path: str, workload: str, precision: str):
         return d.get(workload, {}).get(precision)
     except (OSError, ValueError, KeyError, TypeError, AttributeError):
         return None
+
+
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_frame(dirname: str, frame) -> None:
+    """--dump-outputs: DIR/frame.npy, the float32 frame (H, W, C) — or, for a frame above
+    DUMP_MAX_BYTES (config 5), the rows of a fixed sample of its pixels, (n, C): the same
+    ascending pixel indices (row-major y * W + x, drawn with seed 0) for a given frame size."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    if frame.nbytes > DUMP_MAX_BYTES:
+        px = frame.reshape(-1, frame.shape[-1])
+        n = DUMP_MAX_BYTES // (4 * px.shape[1])
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+        frame = px[idx]
+    np.save(os.path.join(dirname, "frame.npy"), np.ascontiguousarray(frame, dtype=np.float32))
 
 
 def free_port() -> int:
@@ -256,6 +283,15 @@ def main(argv=None) -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: gather check, precision "
+                         "sweep, sun and moving-camera loops, steady-state and window "
+                         "statistics, one-stream kernel time and rooflines, N > 1 side runs, "
+                         "config 5, CPU baseline (off: those fields are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes DIR/frame.npy: the frame the last "
+                         "timed step rendered, float32 (H, W, 3) linear RGB, or (H, W, 4) for "
+                         "--out rgba8; above 48 MB a fixed seeded sample of its pixels, (n, C)")
     ap.add_argument("--config", default="c2", choices=sorted(scenes.CONFIGS))
     ap.add_argument("--precision", default="path64", choices=sorted(capi.PRECISIONS))
     ap.add_argument("--mode", default="tiled", choices=["tiled", "frames"],
@@ -299,17 +335,20 @@ def main(argv=None) -> int:
     ap.add_argument("--sun", action="store_true", help="build-defined sun term (off = parity)")
     ap.add_argument("--steady-frames", type=int, default=200,
                     help="frames of the steady-state loop run right before the warmup and timed "
-                         "region (a side measurement; it also leaves the row order settled)")
+                         "region (it leaves the row order settled; reported with --full)")
     ap.add_argument("--windows", type=int, default=40,
                     help="windows of --steps frames run right before the warmup, each like the "
-                         "timed region (their ms/frame distribution is reported)")
+                         "timed region (their ms/frame distribution is reported with --full; a "
+                         "plain run keeps them within 200 frames each and 2 s in all)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--no-c5", action="store_true",
-                    help="skip the config-5 side run (row-tiled 7680x4320 frames)")
+                    help="--full: skip the config-5 side run (row-tiled 7680x4320 frames)")
     ap.add_argument("--no-sweep", action="store_true",
-                    help="skip the side measurements (precision sweep, sun and moving-camera "
-                         "loops, frame-sharded side run)")
+                    help="--full: skip the side measurements (precision sweep, sun and "
+                         "moving-camera loops, steady state and windows, N > 1 and config-5 "
+                         "side runs)")
     ap.add_argument("--row-feedback", type=int, default=32,
                     help="RT_OPT_ROW_FEEDBACK: refresh interval (frames) of the measured "
                          "tile-row dispatch order, 0 = off (scheduling only)")
@@ -335,6 +374,9 @@ def main(argv=None) -> int:
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "pmc_traffic.json"))
     ap.add_argument("--valu-json", default=os.path.join(REPO, "profiles", "pmc_valu.json"))
     args = ap.parse_args(argv)
+    # a plain run: the headline only.  --full: the side measurements too (--no-sweep trims them)
+    side = args.full and not args.no_sweep
+    condition = side or not args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return supervise(args, sys.argv[1:] if argv is None else list(argv))
@@ -345,6 +387,11 @@ def main(argv=None) -> int:
         print(f"bench: --gpus {args.gpus} but WORLD_SIZE {world} (launch N ranks with --gpus N)",
               file=sys.stderr)
         return 2
+    trims = [o for o, v in (("--no-sweep", args.no_sweep), ("--no-c5", args.no_c5),
+                            ("--no-cpu-baseline", args.no_cpu_baseline)) if v]
+    if trims and not args.full and rank == 0:
+        print(f"bench: {', '.join(trims)} only trim a --full run; a plain run has none of the "
+              f"side measurements and always runs its conditioning loops", file=sys.stderr)
     start_watchdog(args.deadline, rank)
     if os.environ.get("RT_BENCH_TEST_HANG"):   # test hook: a rank stuck before any GPU work
         PHASE[0] = "test hang"
@@ -518,7 +565,7 @@ def main(argv=None) -> int:
     # frames over 2 buffers); EVERY buffer is compared ----
     PHASE[0] = "gather check"
     gather_check = None
-    if tiled_mode:
+    if tiled_mode and args.full:
         ref = None
         nbytes = H * W * (4 if args.out == "rgba8" else 12)
         if rank == 0:
@@ -605,6 +652,8 @@ def main(argv=None) -> int:
         else:   # the torch tiler: the rank fails outright (its peers wait in a collective)
             raise RuntimeError(f"bench rank {rank}: injected failure (--fault-rank)")
 
+    last_slot = [0]   # the torch tiler's frame slot of the latest step (--dump-outputs)
+
     def run_steps(n: int):
         """n consecutive frames, enqueued by ONE C-ABI call (or the torch tiler's loop)."""
         if multi is not None:
@@ -616,7 +665,7 @@ def main(argv=None) -> int:
                                            streams=st_ptrs[:1], nframes=n)
         elif torch_tiled is not None:
             for _ in range(n):
-                torch_tiled.submit()
+                last_slot[0] = torch_tiled.submit()[0]
             torch_tiled.drain()
         else:
             rend.render_device_frames([cam], depth, out_ptrs, prec, flags, out_fmt, row0=row0,
@@ -663,7 +712,7 @@ def main(argv=None) -> int:
     # ---- side measurements (before the timed region; rank 0 reports) ----
     nsw = 200
     sweep, sun_ext, moving = {}, None, None
-    if not args.no_sweep:
+    if side:
         for pname, pc in capi.PRECISIONS.items():
             e0 = torch.cuda.Event(enable_timing=True)
             e1 = torch.cuda.Event(enable_timing=True)
@@ -723,14 +772,14 @@ def main(argv=None) -> int:
     rend.set_option(capi.RT_OPT_ROW_FEEDBACK, 0)
     rend.set_option(capi.RT_OPT_ROW_FEEDBACK, args.row_feedback)
 
-    # ---- steady state: the timed loop itself over 200 frames (a side measurement, before
-    # the warmup).  It also leaves the product path's measured tile-row order settled for
+    # ---- steady state: the timed loop itself over 200 frames, before the warmup (reported
+    # by a full run).  It leaves the product path's measured tile-row order settled for
     # this camera, as in a running frame loop; without it a short timed region (the driver
     # runs 20 steps) spends its first frames on the order's ramp-up (measured: 20-step
     # regions 33-40 us/frame vs 29 over 200 frames) ----
     steady = None
     PHASE[0] = "steady state"
-    if not args.no_sweep:
+    if condition:
         nst = max(1, args.steady_frames)
         torch.cuda.synchronize(dev)
         if multi is not None:
@@ -762,24 +811,32 @@ def main(argv=None) -> int:
     # runs as the next window of the same rhythm: the GPU's clock governor ramps its shader
     # clock over ~20 ms of sustained load (2.2 -> 2.4 GHz measured inside the frames) and a
     # host core that slept clocks down ----
+    # A plain run bounds this conditioning, so that it stays a small part of a run with many
+    # or long steps: windows of at most 200 frames, and as many of them as fit in 2 s at the
+    # steady-state loop's ms/frame (the same figure on every rank).  At the usual 20 to 200
+    # steps of c2 that is every window, as in a full run.
     windows = None
-    if not args.no_sweep and args.windows > 0:
+    if condition and args.windows > 0:
         wms = []
-        for _ in range(args.windows):
+        kw, nwin = args.steps, args.windows
+        if not args.full:
+            kw = min(args.steps, 200)
+            nwin = min(nwin, max(1, int(2e3 / max(1e-6, kw * steady["ms_per_step"]))))
+        for _ in range(nwin):
             hot_sync()
             barrier()
             tw0 = time.perf_counter()
-            run_steps(args.steps)
+            run_steps(kw)
             torch.cuda.synchronize(dev)   # as the timed region ends (see there)
             barrier()
-            wms.append((time.perf_counter() - tw0) / args.steps * 1e3)
+            wms.append((time.perf_counter() - tw0) / kw * 1e3)
         if multi is not None:
             multi.sync()
         tw = torch.tensor(wms, dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(tw, op=dist.ReduceOp.MAX)
         q = sorted(tw.tolist())
-        windows = {"windows": len(q), "frames_per_window": args.steps,
+        windows = {"windows": len(q), "frames_per_window": kw,
                    "ms_per_step_median": round(q[len(q) // 2], 4),
                    "ms_per_step_p10": round(q[int(0.1 * (len(q) - 1))], 4),
                    "ms_per_step_p90": round(q[int(0.9 * (len(q) - 1))], 4),
@@ -819,24 +876,38 @@ def main(argv=None) -> int:
     elapsed_s = float(elapsed.item())
     stream_ms = max(ev0.elapsed_time(e_) for e_ in ev1s) / args.steps
 
+    # ---- --dump-outputs: the frame of the last timed step, as its caller holds it (the
+    # whole frame is on rank 0 in tiled mode; in frames mode rank 0's own frame) ----
+    if args.dump_outputs and rank == 0:
+        PHASE[0] = "dump outputs"
+        if torch_tiled is not None:
+            last = torch_tiled.frame(last_slot[0])
+        else:   # frame f of a call went to buffer f % nbuf
+            last = outs[(args.steps - 1) % nbuf]
+            if args.out == "rgba8":
+                last = last.view(torch.uint8).flatten()[:H * W * 4].view(H, W, 4)
+        dump_frame(args.dump_outputs, last.to(torch.float32).cpu().numpy())
+
     # ---- per-launch kernel time: this rank's rows, one stream, launches back to back ----
     # (after 64 untimed frames of `rend`, whose measured row order the side loops reset)
-    rend.render_device_frames([cam], depth, [out.data_ptr()], prec, flags, out_fmt, row0=row0,
-                              nrows=nrows, streams=[stream.cuda_stream], nframes=64)
-    ek0 = torch.cuda.Event(enable_timing=True)
-    ek1 = torch.cuda.Event(enable_timing=True)
-    nk = max(50, args.steps)
-    ek0.record(stream)
-    rend.render_device_frames([cam], depth, [out.data_ptr()], prec, flags, out_fmt, row0=row0,
-                              nrows=nrows, streams=[stream.cuda_stream], nframes=nk)
-    ek1.record(stream)
-    torch.cuda.synchronize(dev)
-    kernel_ms = ek0.elapsed_time(ek1) / nk
+    kernel_ms = None
+    if args.full:
+        rend.render_device_frames([cam], depth, [out.data_ptr()], prec, flags, out_fmt, row0=row0,
+                                  nrows=nrows, streams=[stream.cuda_stream], nframes=64)
+        ek0 = torch.cuda.Event(enable_timing=True)
+        ek1 = torch.cuda.Event(enable_timing=True)
+        nk = max(50, args.steps)
+        ek0.record(stream)
+        rend.render_device_frames([cam], depth, [out.data_ptr()], prec, flags, out_fmt, row0=row0,
+                                  nrows=nrows, streams=[stream.cuda_stream], nframes=nk)
+        ek1.record(stream)
+        torch.cuda.synchronize(dev)
+        kernel_ms = ek0.elapsed_time(ek1) / nk
 
     # ---- N > 1 side run: the weak (frame-sharded) layout, same frame loop, no collective --
     sharded = None
     PHASE[0] = "side runs"
-    if tiled_mode and world > 1 and not args.no_sweep:
+    if tiled_mode and world > 1 and side:
         # whole frames on every rank: full-size buffers (a non-root rank's `outs` hold a band)
         if full:
             fl_outs = out_ptrs
@@ -869,7 +940,7 @@ def main(argv=None) -> int:
     # ---- N > 1 side run: the same row-tiled frames with the RGBA8 epilogue as transport
     # (4 B/px instead of 12: the root's inbound bytes, which bound config 4, shrink 3x) ----
     tiled8 = None
-    if multi is not None and world > 1 and args.out == "rgb_f32" and not args.no_sweep:
+    if multi is not None and world > 1 and args.out == "rgb_f32" and side:
         n8 = max(50, args.steps)
         multi.render_device_frames([cam], depth, out_ptrs if multi.has_root else [], prec, flags,
                                    capi.RT_OUT_RGBA8, streams=st_ptrs if multi.has_root else st_ptrs[:1],
@@ -895,7 +966,7 @@ def main(argv=None) -> int:
     # the interleaved layout (tile rows dealt round-robin: the sphere cloud's heavy rows are
     # shared; contiguous bands leave one rank 2.7x the average, tools/band_model.py) ----
     c5 = None
-    if multi is not None and not args.no_sweep and args.config != "c5" and not args.no_c5:
+    if multi is not None and side and args.config != "c5" and not args.no_c5:
         c5cfg = scenes.CONFIGS["c5"]
         c5sc = c5cfg.scene()
         c5prims = scenes.to_prims(c5sc)
@@ -964,7 +1035,7 @@ def main(argv=None) -> int:
         value = total_segs * args.steps / elapsed_s / 1e6
         frames_per_step = 1 if tiled_mode else world
         px_step = W * H * frames_per_step
-        kernel_s = kernel_ms * 1e-3
+        kernel_s = kernel_ms * 1e-3 if args.full else None
         out_bytes = nrows * W * (4 if args.out == "rgba8" else 12)
         alg_bytes = out_bytes + scene_bytes(n_sph, n_wall, len(sc))
         tag = cfg.name if not (tiled_mode and world > 1) else "c4"
@@ -996,6 +1067,7 @@ def main(argv=None) -> int:
             "n_gpus": n_ranks,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_step, 4),
             "higher_is_better": True,
             "scaling": "strong" if tiled_mode else "weak",
@@ -1034,7 +1106,7 @@ def main(argv=None) -> int:
             "mpx_per_s": round(px_step * args.steps / elapsed_s / 1e6, 2),
             # one frame (this rank's rows) at a time on one stream (HIP events around
             # back-to-back launches): the per-frame latency the rooflines are priced on
-            "kernel_ms": round(kernel_ms, 4),
+            "kernel_ms": round(kernel_ms, 4) if args.full else None,
             "stream_ms_per_step": round(stream_ms, 4),
             "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
             "timed_edges_us": {"synchronized": round(t_synced * 1e6, 1),
@@ -1048,7 +1120,7 @@ def main(argv=None) -> int:
                 "traffic": traffic,
                 "algorithmic_bytes_per_launch": alg_bytes,
                 "note": "north_star-mandated HBM view; the kernel is FP VALU-bound, see roofline_valu",
-            },
+            } if args.full else None,
             "roofline_valu": {
                 "bound": "valu",
                 "achieved": round(flops / kernel_s / 1e12, 3),
@@ -1061,19 +1133,19 @@ def main(argv=None) -> int:
                               "the kernels cull (tile bins, cone, clusters), so it credits "
                               "work never executed (c5 gives 1.26x peak); `hw` is measured",
                 "hw": valu_hw,
-            },
+            } if args.full else None,
             "cpu_baseline": None,
             "precision_sweep": sweep or None,
             "sun_extension": sun_ext,
             "moving_camera": moving,
-            "steady_state": steady,
-            "window_rhythm": windows,
+            "steady_state": steady if args.full else None,
+            "window_rhythm": windows if args.full else None,
             "frame_sharded": sharded,
             "tiled_rgba8": tiled8,
             "c5_tiled": c5,
             "gather_check": gather_check,
         }
-        if world == 1 and not args.no_cpu_baseline and args.cpu_seconds > 0:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_seconds > 0:
             result["cpu_baseline"] = cpu_baseline(cfg, prims, cam0, depth, flags, args.cpu_seconds)
         print(json.dumps(result), file=json_out, flush=True)
     if multi is not None:

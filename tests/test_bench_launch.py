@@ -85,7 +85,7 @@ def test_world_size_that_disagrees_with_gpus_is_an_error():
     assert "WORLD_SIZE 1" in p.stderr
 
 
-COMMON = ["--steps", "5", "--warmup", "2", "--no-sweep", "--no-cpu-baseline", "--deadline", "200"]
+COMMON = ["--full", "--steps", "5", "--warmup", "2", "--no-sweep", "--no-cpu-baseline", "--deadline", "200"]
 
 
 @pytest.mark.gpu

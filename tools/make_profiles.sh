@@ -11,16 +11,16 @@ ROUND=${ROUND:-r01}; OUT=gpurun_out/prof_$ROUND
 CONFIGS=${CONFIGS:-c2}; PRECS=${PRECS:-path64 f64 f32}
 mkdir -p "$OUT"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -o bench -- \
-    python3 bench.py --steps 200 --warmup 40 --no-cpu-baseline --no-sweep > "$OUT/bench.json" 2> "$OUT/bench.err" \
+    python3 bench.py --full --steps 200 --warmup 40 --no-cpu-baseline --no-sweep > "$OUT/bench.json" 2> "$OUT/bench.err" \
     || { echo "bench trace failed"; exit 1; }
 echo "bench trace ok"
 # the same bench with one frame at a time (every dispatch serial: rocprof's average is then
 # directly the bench's one-stream kernel_ms) and the driver's default command
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_fif1" -o bench -- \
-    python3 bench.py --steps 200 --warmup 40 --no-cpu-baseline --no-sweep --frames-in-flight 1 \
+    python3 bench.py --full --steps 200 --warmup 40 --no-cpu-baseline --no-sweep --frames-in-flight 1 \
     > "$OUT/bench_fif1.json" 2> "$OUT/bench_fif1.err" || { echo "fif1 trace failed"; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_default" -o bench -- \
-    python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" \
+    python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" \
     || { echo "default trace failed"; exit 1; }
 echo "fif1 + default traces ok"
 for cfg in $CONFIGS; do

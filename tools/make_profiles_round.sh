@@ -14,10 +14,10 @@ CONFIGS=${CONFIGS:-c2 c1 c3 c5}; PRECS=${PRECS:-path64}
 mkdir -p "$OUT"
 if [ "${TRACES:-1}" = 1 ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_default" -o bench -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" \
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" \
       || { echo "default trace failed"; exit 1; }
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_fif1" -o bench -- \
-      python3 bench.py --steps 200 --warmup 40 --no-cpu-baseline --no-sweep --frames-in-flight 1 \
+      python3 bench.py --full --steps 200 --warmup 40 --no-cpu-baseline --no-sweep --frames-in-flight 1 \
       > "$OUT/bench_fif1.json" 2> "$OUT/bench_fif1.err" || { echo "fif1 trace failed"; exit 1; }
   echo "traces ok"
 fi
