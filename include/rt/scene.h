@@ -12,7 +12,8 @@
  * What changes is underneath: rt_scene flattens the scene through SceneGeometry::pack()
  * into rt_prim records and renders the frame on the MI355X through the C-ABI
  * (include/rt_capi.h).  SceneGeometry::intersect stays available on the host with the
- * reference's semantics (world distance for spheres, parametric t for walls).
+ * reference's semantics (world distance for spheres, parametric t for walls); batches of
+ * rays go to the GPU through rt_closest_hits and rt_radiance (below).
  */
 #ifndef RT_SCENE_H
 #define RT_SCENE_H
@@ -158,5 +159,22 @@ RtSceneOptions rt_scene_get_options();
  * and RCCL runtimes have initialised, so before their own teardown — never from a static
  * destructor. */
 void rt_scene_shutdown();
+
+/* Batch forms of the reference's other two public functions, on the GPU (rt_trace_rays,
+ * include/rt_capi.h), over the same process-wide one-GPU renderer and RtSceneOptions as
+ * rt_scene (device, flags; precision, with F64 where the option is RT_PREC_MIXED):
+ *   rt_closest_hits()[k] == find_closest_hit(scene, rays[k])            (main.cpp:67-84)
+ *   rt_radiance()[k]     == recursive_ray_tracing(scene, rays[k], remaining_iterations)
+ *                                                                       (main.cpp:89-119)
+ * Collision fields are as find_closest_hit returns them (sphere: world distance and the
+ * un-normalised point - centre; wall: parametric t and its stored normal); a miss has
+ * distance DBL_MAX, hit == false and hit_object_index == -1.  A SceneGeometry subclass
+ * without a GPU record throws std::invalid_argument, as in rt_scene. */
+std::vector<Collision> rt_closest_hits(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                                       const std::vector<ray>& rays);
+std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                             const std::vector<ray>& rays, int remaining_iterations = 10);
+/* One rt_hit record (rt_trace_rays through the C-ABI directly) as the reference's Collision. */
+Collision rt_collision_from_hit(const rt_hit& h);
 
 #endif

@@ -31,7 +31,8 @@ extern "C" {
 #endif
 
 /* Version 2 adds the multi-GPU frame operator (rt_multi_*) and RT_ERR_COMM; every version-1
- * entry point keeps its signature and meaning (the ABI grows additively). */
+ * entry point keeps its signature and meaning (the ABI grows additively).  The ray queries
+ * (rt_hit, rt_trace_rays, rt_trace_rays_device) arrived within version 2: purely additive. */
 #define RT_CAPI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------- */
@@ -337,6 +338,54 @@ int rt_render_device_frames(rt_ctx* ctx, const rt_camera* cams, int32_t ncams, i
                             int32_t nrows, int32_t depth, int32_t precision, uint32_t flags,
                             int32_t out_format, void* const* d_outs, int32_t nouts,
                             void* const* streams, int32_t nstreams, int32_t nframes);
+
+/* ---- ray queries (find_closest_hit, recursive_ray_tracing for caller rays) ---------- */
+/* The reference's find_closest_hit(scene, ray) (main.cpp:67-84) and recursive_ray_tracing(
+ * scene, ray, remaining) (main.cpp:89-119) take any ray, not only a camera's pixel rays:
+ * picking, line-of-sight and collision probes, light probes, a host's own camera models.
+ * These entry points run them on the device for a batch of n rays, one GPU lane per ray.
+ *
+ * rt_hit is the Collision find_closest_hit returns, as plain data.  A miss is main.cpp:70's
+ * placeholder {DBL_MAX, {0,0,0}, -1, 0}, so whole record arrays compare bytewise. */
+typedef struct rt_hit {          /* 40 bytes */
+    double  distance;   /* the value find_closest_hit compares: world distance for a sphere,
+                           parametric t for a wall (the reference's quirk, kept) */
+    double  normal[3];  /* as Collision carries it: unnormalised point - centre for a sphere,
+                           the stored normal for a wall */
+    int32_t index;      /* SCENE index (rt_set_scene order), -1 = miss */
+    int32_t reserved;   /* 0 */
+} rt_hit;
+
+/* origins, directions: n x 3 doubles, row-major; directions are NOT normalised (as in the
+ * reference, where |d| scales a wall's parametric t).  out: n pixels of out_format, ray k's
+ * radiance recursive_ray_tracing(scene, ray k, depth) at pixel k; hits: n records, the
+ * closest hit of each ray's FIRST segment.  Either may be NULL (both: RT_ERR_INVALID_ARG).
+ * With out == NULL the call is the pure find_closest_hit query: one segment per ray, no
+ * shading, no bounce (depth and flags unused; the segment count is n).
+ * Precisions: RT_PREC_F64 op for op; RT_PREC_PATH64 exact paths with fp32 colour (hit records
+ * are the same bits in both); RT_PREC_MIXED is served by the F64 kernels (its contract is
+ * "output == F64"); RT_PREC_F32 returns RT_ERR_UNSUPPORTED.  RT_FLAG_SUN as for frames.
+ * n == 0: RT_OK, nothing launched; n < 0 or n > INT32_MAX: RT_ERR_INVALID_ARG; depth outside
+ * 0..rt_max_depth(): RT_ERR_UNSUPPORTED as for frames; RT_ERR_NO_SCENE before rt_set_scene.
+ * Scenes of RT_OPT_WAVE_CULL_MIN_SPHERES spheres or more cull per wave: by the cone of the
+ * wave's 64 rays when they are coherent, else by each lane's own walk over the sphere
+ * clusters (RT_OPT_CLUSTER_COS), so neighbouring rays of a batch should be neighbours in
+ * space where the caller can arrange it.  The frame-only options (tile bins, eye tables,
+ * mirror bins, row order, row feedback, frame batching) do not apply, and a ray call leaves
+ * their cached state as it was.
+ *
+ * rt_trace_rays: host memory in and out, synchronous (staging buffers in the ctx; stats as
+ * rt_render: ms = device time of the kernel, segments only when count_segments != 0). */
+int rt_trace_rays(rt_ctx* ctx, const double* origins, const double* directions, int64_t n,
+                  int32_t depth, int32_t precision, uint32_t flags, int32_t out_format,
+                  void* out, rt_hit* hits, int32_t count_segments, rt_stats* stats);
+/* The same with every buffer in DEVICE memory, enqueued on `stream` (NULL = the ctx's) without
+ * synchronising; *d_segments (may be NULL) receives += the segment count.  Like
+ * rt_render_device the launch signals the ctx's per-stream event that rt_set_scene and
+ * rt_ctx_destroy wait on. */
+int rt_trace_rays_device(rt_ctx* ctx, const double* d_origins, const double* d_directions, int64_t n,
+                         int32_t depth, int32_t precision, uint32_t flags, int32_t out_format,
+                         void* d_out, rt_hit* d_hits, uint64_t* d_segments, void* stream);
 
 /* ---- multi-GPU frame operator (BASELINE config 4) ----------------------- */
 /* ONE frame split into contiguous row bands (rt_band_rows) over nranks ranks, one GPU each,

@@ -24,6 +24,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -162,6 +163,11 @@ struct rt_ctx {
     void* d_out = nullptr;
     size_t d_out_cap = 0;
     unsigned long long* d_segs = nullptr;
+    // rt_trace_rays' staging buffers: origins then directions; hit records (d_out: colours)
+    void* d_rays = nullptr;
+    size_t d_rays_cap = 0;
+    void* d_hits = nullptr;
+    size_t d_hits_cap = 0;
     // Renders enqueued on caller streams (rt_render_device): per stream, an event recorded
     // behind its latest launch.  rt_set_scene and rt_ctx_destroy wait on every one of them
     // before they overwrite or free the device scene, so a frame still in flight on a
@@ -622,10 +628,9 @@ void frame_boxes(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t 
     p.mir_depth = depth;
 }
 
-rt::KParams make_params(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
-                        int32_t depth, uint32_t flags, int32_t out_format, void* d_out,
-                        unsigned long long* d_segs, int32_t precision) {
-    rt::KParams p{};
+/* The scene's part of the kernel arguments: the sections of the device image, the cluster
+ * set of the precision, the scan choice (wave cull or linear). */
+void scene_params(const rt_ctx* ctx, int32_t precision, rt::KParams& p) {
     const char* base = static_cast<const char*>(ctx->d_scene);
     // section `off` of the device scene (null without one: rt_frame_boxes' host-only use)
     auto at = [base](size_t off) -> const char* { return base ? base + off : nullptr; };
@@ -651,6 +656,13 @@ rt::KParams make_params(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, i
     p.nW = ctx->sc.nW;
     p.int_exp = ctx->sc.int_exp ? 1 : 0;
     p.wave_cull = ctx->sc.nS >= ctx->wave_cull_min ? 1 : 0;
+}
+
+rt::KParams make_params(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
+                        int32_t depth, uint32_t flags, int32_t out_format, void* d_out,
+                        unsigned long long* d_segs, int32_t precision) {
+    rt::KParams p{};
+    scene_params(ctx, precision, p);
     p.W = cam->width;
     p.row0 = row0;
     p.nrows = nrows;
@@ -1186,6 +1198,8 @@ int rt_ctx_destroy(rt_ctx* ctx) {
     if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
     if (ctx->d_scene) (void)hipFree(ctx->d_scene);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
+    if (ctx->d_rays) (void)hipFree(ctx->d_rays);
+    if (ctx->d_hits) (void)hipFree(ctx->d_hits);
     if (ctx->d_segs) (void)hipFree(ctx->d_segs);
     if (ctx->ev_cost) (void)hipEventSynchronize(ctx->ev_cost);
     if (ctx->d_cost) (void)hipFree(ctx->d_cost);
@@ -1908,6 +1922,138 @@ int rt_render(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows, in
     if (st != RT_OK) return st;
     if (bytes > 0)
         RT_HIP(ctx, hipMemcpyAsync(out, ctx->d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned long long hsegs = 0;
+    if (segs)
+        RT_HIP(ctx, hipMemcpyAsync(&hsegs, segs, sizeof hsegs, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) {
+        float ms = 0.f;
+        RT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        stats->ms = ms;
+        stats->segments = hsegs;
+    }
+    return RT_OK;
+}
+
+}  // extern "C"
+
+/* ---- ray batches (rt_trace_rays*) ------------------------------------------------------
+ * find_closest_hit / recursive_ray_tracing for caller rays (rt_rays.hip).  Nothing of a
+ * frame takes part: no camera, pixel boxes, mirror chains, eye tables, row order or row
+ * feedback, so the box cache and the feedback state are neither read nor written. */
+static_assert(sizeof(rt_hit) == sizeof(rt::DevHit) && offsetof(rt_hit, normal) == offsetof(rt::DevHit, normal) &&
+                  offsetof(rt_hit, index) == offsetof(rt::DevHit, index),
+              "rt_hit is the kernels' record");
+
+namespace {
+
+int check_ray_args(const rt_ctx* ctx, const double* origins, const double* directions, int64_t n,
+                   int32_t depth, int32_t precision, int32_t out_format, const void* out,
+                   const void* hits) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (n < 0 || n > INT32_MAX) return RT_ERR_INVALID_ARG;
+    if (!out && !hits) return RT_ERR_INVALID_ARG;
+    if (n > 0 && (!origins || !directions)) return RT_ERR_INVALID_ARG;
+    if (depth < 0) return RT_ERR_INVALID_ARG;
+    if (precision < RT_PREC_F64 || precision > RT_PREC_PATH64) return RT_ERR_INVALID_ARG;
+    if (bytes_per_pixel(out_format) == 0) return RT_ERR_INVALID_ARG;
+    if (!ctx->have_scene) return RT_ERR_NO_SCENE;
+    if (depth > rt::max_depth()) return RT_ERR_UNSUPPORTED;
+    if (precision == RT_PREC_F32) return RT_ERR_UNSUPPORTED;  // no fp32 ray kernels yet
+    return RT_OK;
+}
+
+/* The launch of one batch (n > 0, arguments checked, the ctx's device current). */
+int launch_ray_batch(rt_ctx* ctx, const double* d_origins, const double* d_directions, int64_t n,
+                     int32_t depth, int32_t precision, uint32_t flags, int32_t out_format,
+                     void* d_out, rt_hit* d_hits, unsigned long long* d_segs, hipStream_t hs,
+                     hipEvent_t done) {
+    // MIXED's contract is "output == F64": the F64 kernels serve it
+    const int32_t prec = precision == RT_PREC_MIXED ? RT_PREC_F64 : precision;
+    rt::KParams p{};
+    scene_params(ctx, prec, p);
+    p.depth = depth;
+    p.flags = flags;
+    p.outf = out_format;
+    p.out = d_out;
+    p.segs = d_segs;
+    rt::RayArgs ra{};
+    ra.org = d_origins;
+    ra.dir = d_directions;
+    ra.hits = reinterpret_cast<rt::DevHit*>(d_hits);
+    ra.n = (int32_t)n;
+    ra.shade = d_out ? 1 : 0;
+    const int e = rt::launch_rays(p, ra, prec, hs, done);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_rays");
+    return RT_OK;
+}
+
+/* A staging buffer of the host variant, grown on demand (ctx->stream idle while it moves). */
+int grow(rt_ctx* ctx, void** buf, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return RT_OK;
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (*buf) RT_HIP(ctx, hipFree(*buf));
+    *buf = nullptr;
+    *cap = 0;
+    RT_HIP(ctx, hipMalloc(buf, bytes));
+    *cap = bytes;
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_trace_rays_device(rt_ctx* ctx, const double* d_origins, const double* d_directions,
+                         int64_t n, int32_t depth, int32_t precision, uint32_t flags,
+                         int32_t out_format, void* d_out, rt_hit* d_hits, uint64_t* d_segments,
+                         void* stream) {
+    int st = check_ray_args(ctx, d_origins, d_directions, n, depth, precision, out_format, d_out, d_hits);
+    if (st != RT_OK || n == 0) return st;
+    DeviceGuard dg(ctx->device);
+    RT_HIP(ctx, dg.err);
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    hipEvent_t done = nullptr;
+    st = launch_event(ctx, hs, &done);
+    if (st != RT_OK) return st;
+    return launch_ray_batch(ctx, d_origins, d_directions, n, depth, precision, flags, out_format, d_out,
+                            d_hits, reinterpret_cast<unsigned long long*>(d_segments), hs, done);
+}
+
+int rt_trace_rays(rt_ctx* ctx, const double* origins, const double* directions, int64_t n,
+                  int32_t depth, int32_t precision, uint32_t flags, int32_t out_format, void* out,
+                  rt_hit* hits, int32_t count_segments, rt_stats* stats) {
+    int st = check_ray_args(ctx, origins, directions, n, depth, precision, out_format, out, hits);
+    if (st != RT_OK) return st;
+    if (n == 0) {
+        if (stats) {
+            stats->ms = 0.0;
+            stats->segments = 0;
+        }
+        return RT_OK;
+    }
+    DeviceGuard dg(ctx->device);
+    RT_HIP(ctx, dg.err);
+    const size_t in_bytes = (size_t)n * 3 * sizeof(double);
+    const size_t out_bytes = out ? (size_t)n * (size_t)bytes_per_pixel(out_format) : 0;
+    const size_t hit_bytes = hits ? (size_t)n * sizeof(rt_hit) : 0;
+    if ((st = grow(ctx, &ctx->d_rays, &ctx->d_rays_cap, 2 * in_bytes)) != RT_OK) return st;
+    if ((st = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_bytes)) != RT_OK) return st;
+    if ((st = grow(ctx, &ctx->d_hits, &ctx->d_hits_cap, hit_bytes)) != RT_OK) return st;
+    double* d_o = static_cast<double*>(ctx->d_rays);
+    double* d_d = d_o + (size_t)n * 3;
+    RT_HIP(ctx, hipMemcpyAsync(d_o, origins, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(d_d, directions, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    unsigned long long* segs = count_segments ? ctx->d_segs : nullptr;
+    if (segs) RT_HIP(ctx, hipMemsetAsync(segs, 0, sizeof *segs, ctx->stream));
+    RT_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    st = launch_ray_batch(ctx, d_o, d_d, n, depth, precision, flags, out_format,
+                          out ? ctx->d_out : nullptr, hits ? static_cast<rt_hit*>(ctx->d_hits) : nullptr,
+                          segs, ctx->stream, nullptr);
+    if (st != RT_OK) return st;
+    RT_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    if (out) RT_HIP(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (hits) RT_HIP(ctx, hipMemcpyAsync(hits, ctx->d_hits, hit_bytes, hipMemcpyDeviceToHost, ctx->stream));
     unsigned long long hsegs = 0;
     if (segs)
         RT_HIP(ctx, hipMemcpyAsync(&hsegs, segs, sizeof hsegs, hipMemcpyDeviceToHost, ctx->stream));

@@ -229,6 +229,27 @@ int launch_trace(const KParams& p, int prec, void* stream, void* done_event = nu
 int launch_trace_batch(const KParams* d_tab, const KParams& p0, int nframes, int prec, void* stream,
                        void* done_event);
 int max_depth();
+
+// Ray batches (rt_trace_rays*, rt_rays.hip): one lane per caller ray, ray blockIdx.x * BLOCK +
+// threadIdx.x.  The scene, depth, flags, output format and pointer, segment counter and cull
+// options travel in a KParams whose frame fields (camera, boxes, row order, eye tables) are
+// unused; the rays themselves in RayArgs.
+struct DevHit {  // == rt_hit (rt_capi.h)
+    double distance;
+    double normal[3];
+    int32_t index, reserved;
+};
+static_assert(sizeof(DevHit) == 40, "rt_hit layout");
+struct RayArgs {
+    const double* org;  // [n][3]
+    const double* dir;  // [n][3], not normalised
+    DevHit* hits;       // [n] closest hit of each ray's first segment, may be null
+    int32_t n;
+    int32_t shade;      // 0: hits only (KParams::out unused): one segment per ray, no shading
+};
+// prec: PREC_F64 or PREC_PATH64 (anything else: hipErrorInvalidValue)
+int launch_rays(const KParams& p, const RayArgs& ra, int prec, void* stream, void* done_event);
+
 // Device self-test of the exact fp64 helpers against IEEE operations:
 // which 0 = division (shared reciprocal), 1 = integer-exponent pow vs pow(),
 // 2 = sqrt_e vs sqrt(); adds the number of mismatches (division, sqrt: bitwise;

@@ -126,7 +126,10 @@
 #ifndef RT_STAMP
 #define RT_STAMP 0  // 1 in rt_trace_stamp.hip: the same kernels, recording each wave's cost
 #endif
-#if RT_DIAG && RT_STAMP
+#ifndef RT_RAYS
+#define RT_RAYS 0   // 1 in rt_rays.hip: the device functions alone (namespace rt::kry), for the
+#endif              // ray-batch kernels; no frame kernel or launcher is compiled there
+#if RT_DIAG && (RT_STAMP || RT_RAYS)
 #undef RT_DIAG
 #define RT_DIAG 0
 #endif
@@ -185,6 +188,8 @@ namespace rt {
 // s_memtime costs ~15% at c2 wherever it sits (tools/ab.py), so the plain kernels have none.
 #if RT_STAMP
 namespace kst {
+#elif RT_RAYS
+namespace kry {
 #else
 namespace kno {
 #endif
@@ -2736,6 +2741,7 @@ __device__ __forceinline__ void trace_grid(const KParams& p) {
 #endif
 }
 
+#if !RT_RAYS  // the frame kernels and their launchers (not in rt_rays.hip)
 template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD>
 __global__ void __launch_bounds__(BLOCK)
 __attribute__((amdgpu_waves_per_eu(waves_per_eu<PREC, SUN, INT_EXP, CULL, MAXD>(), 8)))
@@ -3026,10 +3032,13 @@ int launch_unit_max_ns(const uint16_t* cost, int gy, int gx, int ul, uint32_t* u
     return (int)hipGetLastError();
 }
 #endif  // !RT_STAMP
+#endif  // !RT_RAYS
 
-}  // namespace kno / kst
+}  // namespace kno / kst / kry
 
-#if RT_STAMP
+#if RT_RAYS
+// rt_rays.hip defines its kernels and launch_rays behind this file
+#elif RT_STAMP
 int launch_trace_stamped(const KParams& p, int prec, void* stream, void* done_event) {
     return kst::launch_trace_ns(p, prec, stream, done_event);
 }

@@ -37,6 +37,7 @@ struct Global {
     std::vector<double> staging;
     std::vector<rt_prim> uploaded;  // the scene on the device (re-uploaded only on change)
     bool uploaded_tiled = false;    // ... of the tiled (rt_multi) or the one-GPU renderer
+    std::vector<rt_prim> ctx_prims;  // the scene on `ctx` itself (the ray queries always use it)
     bool atexit_set = false;
     // no destructor: a function-static's destructor runs in an order unspecified relative
     // to the HIP and RCCL runtimes' own teardown; rt_scene_shutdown (atexit) releases
@@ -49,6 +50,7 @@ struct Global {
         multi_devices.clear();
         multi_transport = -1;
         uploaded.clear();
+        ctx_prims.clear();
     }
 };
 
@@ -124,6 +126,7 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
         check(rt_ctx_create(g.opts.device, &g.ctx), nullptr, "rt_ctx_create");
         g.ctx_device = g.opts.device;
         g.uploaded.clear();
+        g.ctx_prims.clear();
     }
     register_shutdown(g);
     if (tiled != g.uploaded_tiled) g.uploaded.clear();
@@ -139,6 +142,7 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
         else
             check(rt_set_scene(g.ctx, prims.data(), (int32_t)prims.size()), g.ctx, "rt_set_scene");
         g.uploaded = prims;
+        if (!tiled) g.ctx_prims = prims;
     }
 
     rt_camera c{};
@@ -166,4 +170,87 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
             const double* p = &g.staging[((size_t)i * W + j) * 3];
             frame_buffer.at(i).at(j) = RGB(p[0], p[1], p[2]);  // main.cpp:136 indexing
         }
+}
+
+/* ---- ray queries: find_closest_hit / recursive_ray_tracing for a batch of rays ----------
+ * The one-GPU renderer of rt_scene (RtSceneOptions::device), its scene kept resident the
+ * same way; a row-tiled rt_scene keeps its own renderer beside it. */
+namespace {
+
+/* Flattens the scene (throws for a primitive without a GPU record, before any device work)
+ * and makes it the scene of g.ctx. */
+void ray_scene(Global& g, const std::vector<std::unique_ptr<SceneGeometry>>& scene) {
+    std::vector<rt_prim> prims(scene.size());
+    for (size_t j = 0; j < scene.size(); j++) scene[j]->pack(&prims[j]);
+    if (!g.ctx || g.ctx_device != g.opts.device) {
+        if (g.ctx) rt_ctx_destroy(g.ctx);
+        g.ctx = nullptr;
+        g.ctx_prims.clear();
+        if (!g.uploaded_tiled) g.uploaded.clear();
+        check(rt_ctx_create(g.opts.device, &g.ctx), nullptr, "rt_ctx_create");
+        g.ctx_device = g.opts.device;
+    }
+    register_shutdown(g);
+    // ctx_prims is empty both before the first upload and after an empty scene: upload then
+    if (g.ctx_prims.empty() || prims.size() != g.ctx_prims.size() ||
+        std::memcmp(prims.data(), g.ctx_prims.data(), prims.size() * sizeof(rt_prim)) != 0) {
+        g.ctx_prims.clear();
+        if (!g.uploaded_tiled) g.uploaded.clear();
+        check(rt_set_scene(g.ctx, prims.data(), (int32_t)prims.size()), g.ctx, "rt_set_scene");
+        g.ctx_prims = prims;
+        if (!g.uploaded_tiled) g.uploaded = prims;
+    }
+}
+
+void flatten_rays(const std::vector<ray>& rays, std::vector<double>& o, std::vector<double>& d) {
+    o.resize(rays.size() * 3);
+    d.resize(rays.size() * 3);
+    for (size_t k = 0; k < rays.size(); k++) {
+        const vec3 ro = rays[k].get_origin(), rd = rays[k].get_direction();
+        o[3 * k] = ro.x, o[3 * k + 1] = ro.y, o[3 * k + 2] = ro.z;
+        d[3 * k] = rd.x, d[3 * k + 1] = rd.y, d[3 * k + 2] = rd.z;
+    }
+}
+
+}  // namespace
+
+Collision rt_collision_from_hit(const rt_hit& h) {
+    return Collision(h.distance, vec3(h.normal[0], h.normal[1], h.normal[2]), h.index >= 0,
+                     (int)h.index);
+}
+
+std::vector<Collision> rt_closest_hits(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                                       const std::vector<ray>& rays) {
+    Global& g = global();
+    std::lock_guard<std::mutex> lk(g.mu);
+    ray_scene(g, scene);
+    std::vector<double> o, d;
+    flatten_rays(rays, o, d);
+    std::vector<rt_hit> hits(rays.size());
+    // the hit record does not depend on the precision (F64 and PATH64 share the exact path)
+    check(rt_trace_rays(g.ctx, o.data(), d.data(), (int64_t)rays.size(), 0, RT_PREC_F64, 0,
+                        RT_OUT_RGB_F64, nullptr, hits.data(), 0, nullptr),
+          g.ctx, "rt_trace_rays");
+    std::vector<Collision> out;
+    out.reserve(rays.size());
+    for (const rt_hit& h : hits) out.push_back(rt_collision_from_hit(h));
+    return out;
+}
+
+std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                             const std::vector<ray>& rays, int remaining_iterations) {
+    Global& g = global();
+    std::lock_guard<std::mutex> lk(g.mu);
+    ray_scene(g, scene);
+    std::vector<double> o, d;
+    flatten_rays(rays, o, d);
+    const int prec = g.opts.precision == RT_PREC_MIXED ? RT_PREC_F64 : g.opts.precision;
+    std::vector<double> rgb(rays.size() * 3);
+    check(rt_trace_rays(g.ctx, o.data(), d.data(), (int64_t)rays.size(), remaining_iterations, prec,
+                        g.opts.flags, RT_OUT_RGB_F64, rgb.data(), nullptr, 0, nullptr),
+          g.ctx, "rt_trace_rays");
+    std::vector<RGB> out;
+    out.reserve(rays.size());
+    for (size_t k = 0; k < rays.size(); k++) out.emplace_back(rgb[3 * k], rgb[3 * k + 1], rgb[3 * k + 2]);
+    return out;
 }

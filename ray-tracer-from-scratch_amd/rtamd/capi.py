@@ -117,6 +117,18 @@ class rt_stats(C.Structure):
     _fields_ = [("ms", C.c_double), ("segments", C.c_uint64)]
 
 
+class rt_hit(C.Structure):
+    """find_closest_hit's Collision as plain data (40 bytes); a miss is
+    {DBL_MAX, (0, 0, 0), -1, 0}."""
+    _fields_ = [("distance", C.c_double), ("normal", C.c_double * 3), ("index", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# the same 40-byte layout as a numpy structured dtype (arrays of rt_hit records)
+HIT_DTYPE = np.dtype([("distance", np.float64), ("normal", np.float64, (3,)),
+                      ("index", np.int32), ("reserved", np.int32)])
+
+
 # Every entry point include/rt_capi.h declares: (name, restype, argtypes).
 _dbl3 = C.POINTER(C.c_double)
 SIGNATURES = [
@@ -154,6 +166,13 @@ SIGNATURES = [
     ("rt_render_device_interleaved", C.c_int,
      [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
       C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    # ray queries
+    ("rt_trace_rays", C.c_int,
+     [C.c_void_p, _dbl3, _dbl3, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_int32,
+      C.c_void_p, C.POINTER(rt_hit), C.c_int32, C.POINTER(rt_stats)]),
+    ("rt_trace_rays_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_int32,
+      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # multi-GPU frame operator
     ("rt_multi_unique_id", C.c_int, [C.POINTER(C.c_uint8)]),
     ("rt_multi_create", C.c_int,
@@ -417,6 +436,44 @@ class Renderer:
         check(self.lib.rt_render_device_frames(self.ctx, ca, len(cams), row0, nrows, depth,
                                                precision, flags, out_format, outs, len(d_outs),
                                                sts, len(streams), nframes), self.ctx)
+
+
+    def trace_rays(self, origins, directions, depth: int, precision: int = RT_PREC_F64,
+                   flags: int = 0, out_format: int = RT_OUT_RGB_F64, want_rgb: bool = True,
+                   want_hits: bool = False, count_segments: bool = False):
+        """rt_trace_rays: radiance and / or closest hits of a batch of rays ([n, 3] origins
+        and un-normalised directions), synchronous -> (rgb or None, hits or None, stats).
+        rgb is [n, 3] (or [n, 4] uint8), hits a HIT_DTYPE array.  want_rgb=False is the pure
+        find_closest_hit query (one segment per ray, no shading)."""
+        o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float64).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("origins and directions differ in shape")
+        n = o.shape[0]
+        rgb = hits = None
+        if want_rgb:
+            dt, shape = out_dtype_shape(out_format, 1, n)
+            rgb = np.empty(shape[1:], dtype=dt)
+        if want_hits:
+            hits = np.empty(n, HIT_DTYPE)
+        st = rt_stats()
+        check(self.lib.rt_trace_rays(
+            self.ctx, o.ctypes.data_as(_dbl3), d.ctypes.data_as(_dbl3), n, depth, precision, flags,
+            out_format, rgb.ctypes.data_as(C.c_void_p) if want_rgb else None,
+            hits.ctypes.data_as(C.POINTER(rt_hit)) if want_hits else None,
+            1 if count_segments else 0, C.byref(st)), self.ctx)
+        return rgb, hits, st
+
+    def trace_rays_device(self, d_origins: int, d_directions: int, n: int, depth: int,
+                          d_out: int, d_hits: int = 0, precision: int = RT_PREC_F64,
+                          flags: int = 0, out_format: int = RT_OUT_RGB_F64, d_segments: int = 0,
+                          stream: int = 0) -> None:
+        """rt_trace_rays_device: the same on raw device addresses, enqueued on `stream`
+        without synchronising (d_out or d_hits may be 0, not both)."""
+        check(self.lib.rt_trace_rays_device(
+            self.ctx, C.c_void_p(d_origins or None), C.c_void_p(d_directions or None), n, depth,
+            precision, flags, out_format, C.c_void_p(d_out or None), C.c_void_p(d_hits or None),
+            C.c_void_p(d_segments or None), C.c_void_p(stream or None)), self.ctx)
 
 
 def multi_unique_id() -> bytes:
