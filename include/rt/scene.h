@@ -142,7 +142,11 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
  * every frame row-tiled across those GPUs and gathers it into devices[0] (rt_multi_*,
  * BASELINE config 4; `transport` RT_TRANSPORT_RCCL, or RT_TRANSPORT_COPY, which also takes
  * one GPU listed several times); one entry with RT_TRANSPORT_RCCL_LOOPBACK goes through
- * the same operator with a one-rank communicator.  The frame is bitwise the one-GPU frame. */
+ * the same operator with a one-rank communicator.  The frame is bitwise the one-GPU frame.
+ * `supersample` S in {1, 2, 4, 8} (default 1) makes rt_scene trace S x S rays per pixel and
+ * store their mean (RT_OPT_SUPERSAMPLE, rt_capi.h; the ray queries below ignore it); it is
+ * the one-GPU renderer's: with `devices` selecting the row-tiled operator, or any other
+ * value, rt_scene throws std::invalid_argument before any device work. */
 struct RtSceneOptions {
     int device = 0;
     int precision = RT_PREC_MIXED;
@@ -150,6 +154,7 @@ struct RtSceneOptions {
     unsigned flags = 0;
     std::vector<int> devices;
     int transport = RT_TRANSPORT_RCCL;
+    int supersample = 1;
 };
 void rt_scene_set_options(const RtSceneOptions& opts);
 RtSceneOptions rt_scene_get_options();

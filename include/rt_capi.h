@@ -291,7 +291,37 @@ enum rt_option {
                                          (rt_weighted_band_rows; equal bands while no weights
                                          cover the frame's tile rows).  The gathered frame is
                                          identical. */
-    RT_OPT_CLUSTER_COS = 12           /* C in [-2000, 2000] (default 400): in scenes that use
+    RT_OPT_SUPERSAMPLE = 22,         /* S in {1, 2, 4, 8} (default 1; anything else is
+                                         RT_ERR_INVALID_ARG): rt_render, rt_render_device and
+                                         rt_render_device_frames trace S x S rays per pixel
+                                         and store their mean.  UNLIKE EVERY OTHER OPTION
+                                         THIS ONE CHANGES THE OUTPUT.  cam, row0, nrows, the
+                                         buffer and its format keep their meaning in output
+                                         pixels: pixel (i, j) is the mean of pixels
+                                         [i*S + b][j*S + a], a, b in [0, S), of the frame the
+                                         same call renders for rt_supersample_camera(cam, S)
+                                         (same depth, precision, flags).  Summation: each
+                                         sample's colour widened to fp64, a balanced pairwise
+                                         tree over the S columns (v = v[:, 0::2] + v[:, 1::2],
+                                         log2 S times), then the same over the S rows, times
+                                         1.0 / (S*S), then the format's conversion (the cast,
+                                         or the RGBA8 quantisation of the mean: tone mapping
+                                         after averaging).  The mean is formed inside the
+                                         trace kernel; only width x height pixels are written.
+                                         d_segments and stats->segments count every sample's
+                                         segments.  RT_PREC_MIXED frames are rendered by the
+                                         RT_PREC_F64 kernels (its contract is output == F64).
+                                         RT_OPT_PIXEL_PAIRS is ignored and RT_OPT_ROW_FEEDBACK
+                                         neither samples nor reorders such frames (centre-out
+                                         order, or an rt_set_row_order over the tile rows of
+                                         the S-times larger frame); RT_OPT_FRAME_BATCH
+                                         launches them one at a time.  Not covered:
+                                         rt_render_device_interleaved with nparts > 1 returns
+                                         RT_ERR_UNSUPPORTED while S > 1, and
+                                         rt_multi_set_option refuses S != 1 with
+                                         RT_ERR_UNSUPPORTED.  rt_trace_rays*,
+                                         rt_tile_row_costs and rt_frame_boxes ignore it. */
+    RT_OPT_CLUSTER_COS = 12          /* C in [-2000, 2000] (default 400): in scenes that use
                                          the wave cull, a wave (any precision) whose live
                                          rays' cone has cos(half-angle) < C/1000 tests each
                                          lane's own ray against sphere clusters (boxes of
@@ -529,7 +559,8 @@ int rt_interleaved_rows(int32_t height, int32_t nparts, int32_t part, int32_t* n
 /* rt_render_device for interleaved part `part` of `nparts`: out_frame_rows == 0 stores the
  * part's rows back to back in frame order (rt_interleaved_rows x width pixels in d_out);
  * != 0 stores every row at its frame row (d_out is the whole frame; the other parts' rows
- * are not touched).  nparts == 1 is the whole frame. */
+ * are not touched).  nparts == 1 is the whole frame.  With RT_OPT_SUPERSAMPLE > 1 and
+ * nparts > 1: RT_ERR_UNSUPPORTED. */
 int rt_render_device_interleaved(rt_ctx* ctx, const rt_camera* cam, int32_t nparts, int32_t part,
                                  int32_t depth, int32_t precision, uint32_t flags,
                                  int32_t out_format, void* d_out, int32_t out_frame_rows,
@@ -540,6 +571,15 @@ int rt_render_device_interleaved(rt_ctx* ctx, const rt_camera* cam, int32_t npar
  * height = (int)(image_width / aspect_ratio) exactly as scene.cpp:82. */
 int rt_camera_init(const double position[3], const double lookat[3], const double vup[3],
                    double vfov, double aspect_ratio, double image_width, rt_camera* cam);
+
+/* The camera of RT_OPT_SUPERSAMPLE's S-times larger frame (host only, no device call):
+ * pixel (j*S + a, i*S + b) of *out is sub-sample (a, b) of cam's pixel (j, i) on the regular
+ * S x S grid of sub-pixel centres.  Per component k, in this order (outputs compare
+ * bitwise): dxs = dx[k] / S, dys = dy[k] / S, h = (S - 1) * 0.5,
+ * tl'[k] = (tl[k] - dxs * h) - dys * h, dx'[k] = dxs, dy'[k] = dys; position unchanged,
+ * width' = width * S, height' = height * S.  S = 1 copies cam.  RT_ERR_INVALID_ARG for a
+ * null pointer, S outside {1, 2, 4, 8}, or a product that overflows int32. */
+int rt_supersample_camera(const rt_camera* cam, int32_t s, rt_camera* out);
 
 /* Bytes per pixel of an output format (0 for an unknown format). */
 int32_t rt_out_bytes_per_pixel(int32_t out_format);

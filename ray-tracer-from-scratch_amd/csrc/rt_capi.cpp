@@ -100,6 +100,7 @@ struct rt_ctx {
     // Only the dispatch order changes: every tile is traced once per frame either way.
     int feedback = 32;             // refresh interval in frames, 0 = off
     bool pixel_pairs = RT_PIXEL_PAIRS_DEFAULT;  // RT_OPT_PIXEL_PAIRS
+    int ss_log2 = 0;               // RT_OPT_SUPERSAMPLE: S = 2^ss_log2 rays per pixel side
     uint16_t* d_cost = nullptr;    // device, d_cost_cap entries (one per wave)
     size_t d_cost_cap = 0;
     uint32_t* d_umax = nullptr;    // device, per dispatch unit: its most expensive wave
@@ -307,6 +308,50 @@ int check_render_args(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int
     if (depth > rt::max_depth()) return RT_ERR_UNSUPPORTED;
     if (precision < RT_PREC_F64 || precision > RT_PREC_PATH64) return RT_ERR_INVALID_ARG;
     if (bytes_per_pixel(out_format) == 0) return RT_ERR_INVALID_ARG;
+    return RT_OK;
+}
+
+/* rt_supersample_camera's arithmetic (rt_capi.h: the operation order is part of the ABI). */
+int supersample_camera(const rt_camera* cam, int32_t s, rt_camera* out) {
+    if (!cam || !out || (s != 1 && s != 2 && s != 4 && s != 8)) return RT_ERR_INVALID_ARG;
+    const int64_t w = (int64_t)cam->width * s, h = (int64_t)cam->height * s;
+    if (w > INT32_MAX || w < INT32_MIN || h > INT32_MAX || h < INT32_MIN) return RT_ERR_INVALID_ARG;
+    if (s == 1) {
+        if (out != cam) std::memcpy(out, cam, sizeof *out);
+        return RT_OK;
+    }
+    rt_camera v = *cam;
+    const double S = (double)s, hh = (S - 1.0) * 0.5;
+    for (int k = 0; k < 3; k++) {
+        const double dxs = cam->pixel_delta_x[k] / S, dys = cam->pixel_delta_y[k] / S;
+        v.image_top_left[k] = (cam->image_top_left[k] - dxs * hh) - dys * hh;
+        v.pixel_delta_x[k] = dxs;
+        v.pixel_delta_y[k] = dys;
+    }
+    v.width = (int32_t)w;
+    v.height = (int32_t)h;
+    *out = v;
+    return RT_OK;
+}
+
+/* The frame the kernels trace for a render of rows [row0, row0 + nrows) of cam: the caller's
+ * own, or with RT_OPT_SUPERSAMPLE the S-times larger one (rt_supersample_camera, rows
+ * row0*S .. ).  Every internal step after the argument checks works on it. */
+struct VirtFrame {
+    rt_camera vcam;
+    const rt_camera* cam;
+    int32_t row0, nrows;
+};
+int virt_frame(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows, VirtFrame& v) {
+    v.cam = cam;
+    v.row0 = row0;
+    v.nrows = nrows;
+    if (!ctx->ss_log2) return RT_OK;
+    const int st = supersample_camera(cam, 1 << ctx->ss_log2, &v.vcam);
+    if (st != RT_OK) return st;
+    v.cam = &v.vcam;
+    v.row0 = row0 << ctx->ss_log2;   // <= height * S, which fits (checked above)
+    v.nrows = nrows << ctx->ss_log2;
     return RT_OK;
 }
 
@@ -660,9 +705,10 @@ void scene_params(const rt_ctx* ctx, int32_t precision, rt::KParams& p) {
 
 rt::KParams make_params(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
                         int32_t depth, uint32_t flags, int32_t out_format, void* d_out,
-                        unsigned long long* d_segs, int32_t precision) {
+                        unsigned long long* d_segs, int32_t precision, int32_t ss_log2 = 0) {
     rt::KParams p{};
     scene_params(ctx, precision, p);
+    p.ss_log2 = ss_log2;  // cam, row0, nrows: the S-times larger frame's (virt_frame)
     p.W = cam->width;
     p.row0 = row0;
     p.nrows = nrows;
@@ -677,7 +723,7 @@ rt::KParams make_params(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, i
     }
     p.out = d_out;
     p.segs = d_segs;
-    p.pairs = ctx->pixel_pairs ? 1 : 0;
+    p.pairs = (ctx->pixel_pairs && !ss_log2) ? 1 : 0;  // (one sample per lane when resolving)
     p.stats = ctx->d_stats;
     // eye tables (rt_device.h) for the linear-scan kernels: the same fp64 operations, in
     // the same order, as sphere_exact / wall_exact on a ray starting at cam->position
@@ -1085,6 +1131,10 @@ const char* rt_last_hip_error(const rt_ctx* ctx) { return ctx ? ctx->last_err : 
 
 int32_t rt_out_bytes_per_pixel(int32_t out_format) { return bytes_per_pixel(out_format); }
 
+int rt_supersample_camera(const rt_camera* cam, int32_t s, rt_camera* out) {
+    return supersample_camera(cam, s, out);
+}
+
 int32_t rt_max_depth(void) { return rt::max_depth(); }
 
 int32_t rt_tile_rows(void) { return rt::TILE_H; }
@@ -1307,6 +1357,10 @@ int rt_set_option(rt_ctx* ctx, int32_t option, int64_t value) {
             if (value != 0 && value != 1) return RT_ERR_INVALID_ARG;
             ctx->pixel_pairs = value == 1;
             return RT_OK;
+        case RT_OPT_SUPERSAMPLE:
+            if (value != 1 && value != 2 && value != 4 && value != 8) return RT_ERR_INVALID_ARG;
+            ctx->ss_log2 = value == 8 ? 3 : (value == 4 ? 2 : (value == 2 ? 1 : 0));
+            return RT_OK;
         case RT_OPT_ROW_FEEDBACK_EMA:
             if (value < 0 || value > 95) return RT_ERR_INVALID_ARG;
             ctx->fb_ema = (int)value;
@@ -1436,7 +1490,7 @@ static int prepare_rows(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t
             p.row_perm_n = gy;
             std::memcpy(p.row_perm, ctx->row_perm.data(), gy * sizeof(int16_t));
         }
-    } else if (ctx->feedback > 0 && ctx->fb_band == band && !ctx->fb_perm.empty()) {
+    } else if (ctx->feedback > 0 && !p.ss_log2 && ctx->fb_band == band && !ctx->fb_perm.empty()) {
         const int nu = gy << ctx->fb_units_log2;
         if ((int)ctx->fb_perm.size() == nu && nu <= rt::ROW_PERM_MAX) {
             p.row_units_log2 = ctx->fb_units_log2;
@@ -1448,6 +1502,7 @@ static int prepare_rows(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t
     p.tile_cost = nullptr;
     if (ctx->feedback <= 0 || !ctx->row_perm.empty() || gy > rt::ROW_PERM_MAX || ctx->cost_pending)
         return RT_OK;
+    if (p.ss_log2) return RT_OK;  // supersampled frames are never sampled (no stamped kernels)
     if (!(ctx->fb_band == band)) {
         ctx->warm_left = ctx->fb_warm;  // a new band or scene: the first snapshot, then the warm ones
     } else if (ctx->warm_left > 0) {
@@ -1578,9 +1633,11 @@ void prep_main(rt_ctx* ctx) {
                    !q.stop.load(std::memory_order_acquire))
                 std::this_thread::yield();
             if (q.stop.load(std::memory_order_acquire)) break;
+            VirtFrame v;  // (cannot fail: the batch's frames were checked before it was posted)
+            if (virt_frame(ctx, &q.cams[f % q.ncams], q.row0, q.nrows, v) != RT_OK) v.nrows = 0;
             q.slot[f % rt_ctx::Prep::RING] =
-                make_params(ctx, &q.cams[f % q.ncams], q.row0, q.nrows, q.depth, q.flags, q.out_format,
-                            q.d_outs[f % q.nouts], nullptr, q.precision);
+                make_params(ctx, v.cam, v.row0, v.nrows, q.depth, q.flags, q.out_format,
+                            q.d_outs[f % q.nouts], nullptr, q.precision, ctx->ss_log2);
             q.produced.store(f + 1, std::memory_order_release);
         }
         q.done.store(seen, std::memory_order_release);
@@ -1651,6 +1708,14 @@ static int render_device_impl(rt_ctx* ctx, const rt_camera* cam, int32_t row0, i
     int st = check_render_args(ctx, cam, row0, nrows, depth, precision, out_format);
     if (st != RT_OK) return st;
     if (!d_out && nrows > 0 && cam->width > 0) return RT_ERR_INVALID_ARG;
+    if (ctx->ss_log2 && nparts > 1) return RT_ERR_UNSUPPORTED;  // contiguous bands only
+    // from here on: the frame the kernels trace (RT_OPT_SUPERSAMPLE: S times larger)
+    VirtFrame vf;
+    st = virt_frame(ctx, cam, row0, nrows, vf);
+    if (st != RT_OK) return st;
+    cam = vf.cam;
+    row0 = vf.row0;
+    nrows = vf.nrows;
     // the ctx's buffers (row feedback) and the launch belong to ctx->device, whatever
     // device the caller has current
     DeviceGuard dg(ctx->device);
@@ -1661,7 +1726,8 @@ static int render_device_impl(rt_ctx* ctx, const rt_camera* cam, int32_t row0, i
     rt::KParams p = pre ? *pre
                         : make_params(ctx, cam, nparts > 1 ? 0 : row0, nparts > 1 ? cam->height : nrows,
                                       depth, flags, out_format, d_out,
-                                      reinterpret_cast<unsigned long long*>(d_segments), precision);
+                                      reinterpret_cast<unsigned long long*>(d_segments), precision,
+                                      ctx->ss_log2);
     if (nparts > 1) {
         p.row0 = 0;
         p.nrows = nrows;
@@ -1776,16 +1842,20 @@ static int launch_frame_groups(rt_ctx* ctx, const rt_camera* cams, int32_t ncams
             rt::KParams& p = grp[n];
             p = q.slot[f % rt_ctx::Prep::RING];
             q.consumed.store(f + 1, std::memory_order_release);
-            const rt_camera* cam = &cams[f % ncams];
-            st = prepare_rows(ctx, cam, row0, nrows, hs, p);
+            VirtFrame vf;
+            st = virt_frame(ctx, &cams[f % ncams], row0, nrows, vf);
+            if (st != RT_OK) break;
+            const rt_camera* cam = vf.cam;
+            st = prepare_rows(ctx, cam, vf.row0, vf.nrows, hs, p);
             if (st != RT_OK) break;
             const bool other_grid = n > 0 && (p.W != grp[0].W || p.nrows != grp[0].nrows ||
                                               p.row_units_log2 != grp[0].row_units_log2);
-            if (p.tile_cost || other_grid) {
+            // (no table kernels for the cull, pair and supersample paths: one launch each)
+            if (p.tile_cost || other_grid || p.wave_cull || p.pairs || p.ss_log2) {
                 // this frame alone (after the frames grouped so far), through the per-frame path
                 const rt::KParams one = p;
                 st = launch_group(ctx, s, n, cam0, row0, nrows, precision, hs);
-                if (st == RT_OK) st = launch_prepared(ctx, cam, row0, nrows, one, precision, hs);
+                if (st == RT_OK) st = launch_prepared(ctx, cam, vf.row0, vf.nrows, one, precision, hs);
                 n = 0;
                 f++;
                 break;
@@ -1910,8 +1980,16 @@ int rt_render(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows, in
     }
     unsigned long long* segs = count_segments ? ctx->d_segs : nullptr;
     if (segs) RT_HIP(ctx, hipMemsetAsync(segs, 0, sizeof *segs, ctx->stream));
+    // host staging above is the output frame's; the kernels trace the (RT_OPT_SUPERSAMPLE:
+    // S times larger) frame below
+    VirtFrame vf;
+    st = virt_frame(ctx, cam, row0, nrows, vf);
+    if (st != RT_OK) return st;
+    cam = vf.cam;
+    row0 = vf.row0;
+    nrows = vf.nrows;
     rt::KParams p = make_params(ctx, cam, row0, nrows, depth, flags, out_format,
-                                ctx->d_out, segs, precision);
+                                ctx->d_out, segs, precision, ctx->ss_log2);
     st = prepare_rows(ctx, cam, row0, nrows, ctx->stream, p);
     if (st != RT_OK) return st;
     RT_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));

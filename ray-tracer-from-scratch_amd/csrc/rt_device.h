@@ -213,6 +213,11 @@ struct KParams {
     // frame's tile rows tphase, tphase + tstride, ... (nrows = their pixel rows, row0 = 0);
     // frame_h = frame height; out_frame = store at frame rows instead of back to back
     int32_t tstride, tphase, frame_h, out_frame;
+    // RT_OPT_SUPERSAMPLE: S = 2^ss_log2 (0 = off).  W, row0, nrows and the camera are the
+    // S-times larger frame's; the kernel stores the mean of each S x S square of its pixels
+    // at row (band row >> ss_log2), column (x >> ss_log2) of an output W >> ss_log2 wide
+    // (rt_trace.hip ss_resolve).  Contiguous bands only.
+    int32_t ss_log2;
 };
 // by-value kernel arguments of up to 16 KB arrive intact (tools/ubench/kernarg_size.hip,
 // kernarg_stale.hip: consistent across back-to-back launches)

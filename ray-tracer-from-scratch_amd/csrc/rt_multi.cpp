@@ -1815,6 +1815,12 @@ int rt_multi_set_scene(rt_multi* m, const rt_prim* prims, int32_t n) {
 
 int rt_multi_set_option(rt_multi* m, int32_t option, int64_t value) {
     if (!m) return RT_ERR_INVALID_ARG;
+    if (option == RT_OPT_SUPERSAMPLE) {
+        // the band exchange sizes and gathers output rows of unsampled frames only; S = 1 is
+        // every rank's default (invalid values keep rt_set_option's status)
+        if (value != 1 && value != 2 && value != 4 && value != 8) return RT_ERR_INVALID_ARG;
+        return value == 1 ? RT_OK : RT_ERR_UNSUPPORTED;
+    }
     if (option == RT_OPT_MULTI_FAULT) {
         if (value != 0 && value != 1) return RT_ERR_INVALID_ARG;
         m->fault_next = value == 1;

@@ -2614,8 +2614,68 @@ __device__ __forceinline__ BandRow band_row(const KParams& p, int trow, int sr) 
     return b;
 }
 
-/* One tile per wave: tile column bx, tile row trow (after the row order), gx tile columns. */
-template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD>
+/* RT_OPT_SUPERSAMPLE's resolve (KParams::ss_log2 = k, S = 2^k): the wave's 8x8 square holds
+ * the S x S samples of (8/S)^2 output pixels, sample (a, b) of a pixel at lane bits 0..k-1 (a)
+ * and 3..3+k-1 (b).  An xor-butterfly over the column bits, then the row bits, is the
+ * balanced pairwise tree of rt_capi.h (v[:, 0::2] + v[:, 1::2] repeated, then rows): fp64
+ * addition is commutative, so every lane of a square ends with the same bits whichever half
+ * of a pair it was, and a band that cuts a tile elsewhere than the full frame does stores the
+ * same bytes.  Runs with all 64 lanes active (cross-lane reads of inactive lanes are
+ * undefined): callers keep it outside any `if (valid)`.  1 / S^2 is a power of two, so the
+ * final product is exact.
+ * Lane xor 1, 2 and 8 are DPP moves (quad_perm, row_ror:8: no LDS round trip).  Xor 4 only
+ * occurs at k = 3, after xor 1 and 2 made each quad uniform, where the half-row mirror
+ * (lane i <-> 7 - i) reads the same value as lane i ^ 4 would.  Xor 16 and 32 go through
+ * ds_bpermute.  The three channels take each step together, so a step costs one wait. */
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xF, 0xF, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xF, 0xF, false);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ void ss_resolve(int k, double& cr, double& cg, double& cb) {
+    if (k >= 1) {  // columns: lane ^ 1
+        cr += dpp_d<0xB1>(cr);
+        cg += dpp_d<0xB1>(cg);
+        cb += dpp_d<0xB1>(cb);
+    }
+    if (k >= 2) {  // lane ^ 2
+        cr += dpp_d<0x4E>(cr);
+        cg += dpp_d<0x4E>(cg);
+        cb += dpp_d<0x4E>(cb);
+    }
+    if (k >= 3) {  // lane ^ 4 (quads uniform: the half-row mirror)
+        cr += dpp_d<0x141>(cr);
+        cg += dpp_d<0x141>(cg);
+        cb += dpp_d<0x141>(cb);
+    }
+    if (k >= 1) {  // rows: lane ^ 8
+        cr += dpp_d<0x128>(cr);
+        cg += dpp_d<0x128>(cg);
+        cb += dpp_d<0x128>(cb);
+    }
+    if (k >= 2) {  // lane ^ 16
+        const double a = __shfl_xor(cr, 16, 64), b = __shfl_xor(cg, 16, 64), c = __shfl_xor(cb, 16, 64);
+        cr += a;
+        cg += b;
+        cb += c;
+    }
+    if (k >= 3) {  // lane ^ 32
+        const double a = __shfl_xor(cr, 32, 64), b = __shfl_xor(cg, 32, 64), c = __shfl_xor(cb, 32, 64);
+        cr += a;
+        cg += b;
+        cb += c;
+    }
+    const double inv = __longlong_as_double((long long)(1023 - 2 * k) << 52);  // 1 / S^2
+    cr *= inv;
+    cg *= inv;
+    cb *= inv;
+}
+
+/* One tile per wave: tile column bx, tile row trow (after the row order), gx tile columns.
+ * SS: the tile is 8x8 samples of a supersampled frame, resolved before the store. */
+template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD, bool SS = false>
 __device__ __forceinline__ void trace_tile(const KParams& p, int bx, int trow, int gx,
                                            uint64_t braw) {
 #if RT_WAVE_TIMES
@@ -2632,7 +2692,22 @@ __device__ __forceinline__ void trace_tile(const KParams& p, int bx, int trow, i
     // every lane runs the (converged) bounce loop; only valid lanes trace and store
     // the store's coordinates (see RT_STORE_RECOMPUTE)
     auto store = [&](double cr, double cg, double cb) __attribute__((always_inline)) {
-        if (RT_STORE_RECOMPUTE && CULL && BLOCK == 64) {  // (linear kernels: no spill, A/B +1..12%)
+        if constexpr (SS) {
+            // Invariant: the frame's width and the band's row count are multiples of S and a
+            // wave's square starts at multiples of 8, so the S x S samples of an output pixel
+            // are all valid or all invalid.  Invalid lanes hold garbage, which therefore only
+            // ever mixes into squares that are not stored.
+            const int k = p.ss_log2, sm = (1 << k) - 1;
+            ss_resolve(k, cr, cg, cb);  // every lane, before any divergence
+            // coordinates formed again from the tile, as the cull kernels' store below: here
+            // in the linear kernels too, where it keeps them out of scratch (`make asm`)
+            const bool recompute = RT_STORE_RECOMPUTE && BLOCK == 64;
+            const int ls = recompute ? lane_mbcnt() : lane;
+            const int xs = recompute ? bx * TILE_W + (ls & 7) : x;
+            const BandRow bs = recompute ? band_row(p, trow, ls >> 3) : br;
+            if (xs < p.W && bs.ok && (ls & sm) == 0 && ((ls >> 3) & sm) == 0)
+                store_px(p, (size_t)(bs.out >> k) * (size_t)(p.W >> k) + (size_t)(xs >> k), cr, cg, cb);
+        } else if (RT_STORE_RECOMPUTE && CULL && BLOCK == 64) {  // (linear kernels: no spill, A/B +1..12%)
             const int l2 = lane_mbcnt();
             const int xs = bx * TILE_W + (l2 & 7);
             const BandRow bs = band_row(p, trow, l2 >> 3);
@@ -2691,7 +2766,7 @@ __device__ __forceinline__ void trace_tile(const KParams& p, int bx, int trow, i
 
 
 /* One workgroup of a frame's grid (x: tile column or part of one, y: dispatch unit). */
-template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD>
+template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD, bool SS = false>
 __device__ __forceinline__ void trace_grid(const KParams& p) {
     // workgroup row -> dispatch unit (a tile row, or a part of one: KParams::row_units_log2)
     // the primary pixel boxes (one per lane; wave-start load, used after ray generation)
@@ -2728,25 +2803,25 @@ __device__ __forceinline__ void trace_grid(const KParams& p) {
     const int u1 = tile_row(p, j1, n_units);
     const int bx0 = ((u & ((1 << ul) - 1)) * (int)gridDim.x) + (int)blockIdx.x;
     const int bx1 = ((u1 & ((1 << ul) - 1)) * (int)gridDim.x) + (int)blockIdx.x;
-    trace_tile<PREC, SUN, INT_EXP, CULL, MAXD>(p, bx0, u >> ul, gx, braw);
+    trace_tile<PREC, SUN, INT_EXP, CULL, MAXD, SS>(p, bx0, u >> ul, gx, braw);
     if (j1 > (int)blockIdx.y)
-        trace_tile<PREC, SUN, INT_EXP, CULL, MAXD>(p, bx1, u1 >> ul, gx,
-                                                   (RT_EARLY_LOADS >= 2 && !CULL) ? box_load_primary(p) : 0);
+        trace_tile<PREC, SUN, INT_EXP, CULL, MAXD, SS>(p, bx1, u1 >> ul, gx,
+                                                       (RT_EARLY_LOADS >= 2 && !CULL) ? box_load_primary(p) : 0);
 #else
     const int bx = ((u & ((1 << ul) - 1)) * (int)gridDim.x) + (int)blockIdx.x;
     // the last part of a row may be short (wave-uniform): such a wave's lanes are all
     // invalid (x >= W), so it can also run through with nothing to trace or store
     if (!RT_EARLY_LOADS && bx >= gx) return;
-    trace_tile<PREC, SUN, INT_EXP, CULL, MAXD>(p, bx, u >> ul, gx, braw);
+    trace_tile<PREC, SUN, INT_EXP, CULL, MAXD, SS>(p, bx, u >> ul, gx, braw);
 #endif
 }
 
 #if !RT_RAYS  // the frame kernels and their launchers (not in rt_rays.hip)
-template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD>
+template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD, bool SS = false>
 __global__ void __launch_bounds__(BLOCK)
 __attribute__((amdgpu_waves_per_eu(waves_per_eu<PREC, SUN, INT_EXP, CULL, MAXD>(), 8)))
 k_trace(KParams p) {
-    trace_grid<PREC, SUN, INT_EXP, CULL, MAXD>(p);
+    trace_grid<PREC, SUN, INT_EXP, CULL, MAXD, SS>(p);
 }
 
 #if !RT_STAMP
@@ -2824,11 +2899,11 @@ static hipError_t launch_pair(const KParams& p, dim3 grid, hipStream_t st, hipEv
 }
 #endif  // RT_WAVES_PER_BLOCK == 1 && !RT_TILE_PAIRS
 
-template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD>
+template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD, bool SS>
 static void launch_one(const KParams& p, dim3 grid, hipStream_t st, hipEvent_t done,
                        const KParams* tab) {
 #if !RT_STAMP
-    if constexpr (!CULL) {
+    if constexpr (!CULL && !SS) {
         if (tab) {  // grid.z frames, their arguments in the device table
             hipExtLaunchKernelGGL((k_trace_tab<PREC, SUN, INT_EXP, MAXD>), grid, dim3(BLOCK), 0, st,
                                   nullptr, done, 0, (uint64_t)(uintptr_t)tab);
@@ -2837,55 +2912,55 @@ static void launch_one(const KParams& p, dim3 grid, hipStream_t st, hipEvent_t d
     }
 #endif
     if (done)
-        hipExtLaunchKernelGGL((k_trace<PREC, SUN, INT_EXP, CULL, MAXD>), grid, dim3(BLOCK), 0, st,
+        hipExtLaunchKernelGGL((k_trace<PREC, SUN, INT_EXP, CULL, MAXD, SS>), grid, dim3(BLOCK), 0, st,
                               nullptr, done, 0, p);
     else
-        hipLaunchKernelGGL((k_trace<PREC, SUN, INT_EXP, CULL, MAXD>), grid, dim3(BLOCK), 0, st, p);
+        hipLaunchKernelGGL((k_trace<PREC, SUN, INT_EXP, CULL, MAXD, SS>), grid, dim3(BLOCK), 0, st, p);
 }
-template <int PREC, bool SUN, bool INT_EXP, bool CULL>
+template <int PREC, bool SUN, bool INT_EXP, bool CULL, bool SS>
 static hipError_t launch_depth(const KParams& p, dim3 grid, hipStream_t st, hipEvent_t done,
                                const KParams* tab) {
     if constexpr (RT_AB_SLIM && (PREC != PREC_PATH64 || SUN)) {
         return hipErrorInvalidValue;
     } else if constexpr (RT_AB_SLIM) {
         if (p.depth <= MAXD_SMALL)
-            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_SMALL>(p, grid, st, done, tab);
+            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_SMALL, SS>(p, grid, st, done, tab);
         else if (p.depth <= MAXD_MID)
-            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_MID>(p, grid, st, done, tab);
+            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_MID, SS>(p, grid, st, done, tab);
         else
             return hipErrorInvalidValue;
         return hipGetLastError();
     } else {
         if (p.depth <= MAXD_SMALL)
-            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_SMALL>(p, grid, st, done, tab);
+            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_SMALL, SS>(p, grid, st, done, tab);
         else if (p.depth <= MAXD_MID)
-            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_MID>(p, grid, st, done, tab);
+            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_MID, SS>(p, grid, st, done, tab);
         else if (p.depth <= MAXD_REF)
-            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_REF>(p, grid, st, done, tab);
+            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_REF, SS>(p, grid, st, done, tab);
         else
-            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_LARGE>(p, grid, st, done, tab);
+            launch_one<PREC, SUN, INT_EXP, CULL, MAXD_LARGE, SS>(p, grid, st, done, tab);
         return hipGetLastError();
     }
 }
-template <int PREC, bool SUN, bool INT_EXP>
+template <int PREC, bool SUN, bool INT_EXP, bool SS>
 static hipError_t launch_cull(const KParams& p, dim3 grid, hipStream_t st, hipEvent_t done,
                               const KParams* tab) {
     if (tab && p.wave_cull) return hipErrorNotSupported;  // no table kernels for the cull path
-    return p.wave_cull ? launch_depth<PREC, SUN, INT_EXP, true>(p, grid, st, done, tab)
-                       : launch_depth<PREC, SUN, INT_EXP, false>(p, grid, st, done, tab);
+    return p.wave_cull ? launch_depth<PREC, SUN, INT_EXP, true, SS>(p, grid, st, done, tab)
+                       : launch_depth<PREC, SUN, INT_EXP, false, SS>(p, grid, st, done, tab);
 }
-template <int PREC>
+template <int PREC, bool SS = false>
 static hipError_t launch_prec(const KParams& p, dim3 grid, hipStream_t st, hipEvent_t done,
                               const KParams* tab = nullptr) {
     if constexpr (PREC == PREC_F64 || PREC == PREC_MIXED) {
         if (p.flags & FLAG_SUN)
-            return p.int_exp ? launch_cull<PREC, true, true>(p, grid, st, done, tab)
-                             : launch_cull<PREC, true, false>(p, grid, st, done, tab);
-        return p.int_exp ? launch_cull<PREC, false, true>(p, grid, st, done, tab)
-                         : launch_cull<PREC, false, false>(p, grid, st, done, tab);
+            return p.int_exp ? launch_cull<PREC, true, true, SS>(p, grid, st, done, tab)
+                             : launch_cull<PREC, true, false, SS>(p, grid, st, done, tab);
+        return p.int_exp ? launch_cull<PREC, false, true, SS>(p, grid, st, done, tab)
+                         : launch_cull<PREC, false, false, SS>(p, grid, st, done, tab);
     } else {
-        return (p.flags & FLAG_SUN) ? launch_cull<PREC, true, true>(p, grid, st, done, tab)
-                                    : launch_cull<PREC, false, true>(p, grid, st, done, tab);
+        return (p.flags & FLAG_SUN) ? launch_cull<PREC, true, true, SS>(p, grid, st, done, tab)
+                                    : launch_cull<PREC, false, true, SS>(p, grid, st, done, tab);
     }
 }
 
@@ -2910,7 +2985,7 @@ int launch_trace_ns(const KParams& p, int prec, void* stream, void* done_event,
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipEvent_t done = static_cast<hipEvent_t>(done_event);
     if (d_tab) {  // a batch of frames: the table kernels (linear scan, one pixel per lane)
-        if (RT_TILE_PAIRS || p.wave_cull || p.pairs) return (int)hipErrorNotSupported;
+        if (RT_TILE_PAIRS || p.wave_cull || p.pairs || p.ss_log2) return (int)hipErrorNotSupported;
         switch (prec) {
             case PREC_F64: return (int)launch_prec<PREC_F64>(p, grid, st, done, d_tab);
             case PREC_F32: return (int)launch_prec<PREC_F32>(p, grid, st, done, d_tab);
@@ -2918,6 +2993,24 @@ int launch_trace_ns(const KParams& p, int prec, void* stream, void* done_event,
             case PREC_PATH64: return (int)launch_prec<PREC_PATH64>(p, grid, st, done, d_tab);
             default: return (int)hipErrorInvalidValue;
         }
+    }
+    if (p.ss_log2) {
+        // RT_OPT_SUPERSAMPLE: the resolving variants, one pixel (sample) per lane; contiguous
+        // bands, k in 1..3.  MIXED's contract is output == F64: the F64 kernels serve it.
+        // (Row feedback never samples such a frame, so the stamped library has none.)
+#if !RT_STAMP
+        if (p.ss_log2 < 0 || p.ss_log2 > 3 || p.tstride > 1 || ((p.W | p.nrows) & ((1 << p.ss_log2) - 1)))
+            return (int)hipErrorInvalidValue;
+        switch (prec) {
+            case PREC_F64:
+            case PREC_MIXED: return (int)launch_prec<PREC_F64, true>(p, grid, st, done);
+            case PREC_F32: return (int)launch_prec<PREC_F32, true>(p, grid, st, done);
+            case PREC_PATH64: return (int)launch_prec<PREC_PATH64, true>(p, grid, st, done);
+            default: return (int)hipErrorInvalidValue;
+        }
+#else
+        return (int)hipErrorNotSupported;
+#endif
     }
     // two pixels per lane exist only in one-wave (8x8 tile) builds: the pair kernel is not
     // instantiated for RT_WAVES_PER_BLOCK > 1 or RT_TILE_PAIRS (RT_OPT_PIXEL_PAIRS ignored)

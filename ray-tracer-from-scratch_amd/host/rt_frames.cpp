@@ -16,10 +16,13 @@
  *
  *   rt_frames [--frames N] [--keys wwaassdd] [--width W] [--depth D] [--precision f64|mixed|
  *             path64|f32] [--scene default|synthetic:S,W[,seed]] [--ppm file] [--gpu-surface]
+ *             [--supersample 1|2|4|8]
  *
  * --gpu-surface replaces rt_scene + the host packing loop by one rt_render with the
  * kernel's RT_OUT_RGBA8_WRAP epilogue: the same bytes main.cpp:345 produces, highlights
  * above 1.0 wrapping modulo 256 as the reference's x86-64 build does.
+ * --supersample S traces S x S rays per pixel and stores their mean (RT_OPT_SUPERSAMPLE;
+ * not in the reference: anti-aliased frames), on either path.
  */
 #include <chrono>
 #include <cmath>
@@ -48,6 +51,7 @@ struct Args {
     std::string scene = "default";
     std::string ppm;
     bool gpu_surface = false;
+    int supersample = 1;
 };
 
 int parse_precision(const std::string& s) {
@@ -78,6 +82,13 @@ Args parse(int argc, char** argv) {
         else if (o == "--scene") a.scene = val();
         else if (o == "--ppm") a.ppm = val();
         else if (o == "--gpu-surface") a.gpu_surface = true;
+        else if (o == "--supersample") {
+            a.supersample = std::atoi(val().c_str());
+            if (a.supersample != 1 && a.supersample != 2 && a.supersample != 4 && a.supersample != 8) {
+                std::fprintf(stderr, "--supersample takes 1, 2, 4 or 8\n");
+                std::exit(2);
+            }
+        }
         else {
             std::fprintf(stderr, "unknown option %s\n", o.c_str());
             std::exit(2);
@@ -158,6 +169,7 @@ int main(int argc, char** argv) {
     RtSceneOptions opts = rt_scene_get_options();
     opts.depth = a.depth;
     opts.precision = a.precision;
+    opts.supersample = a.supersample;
     rt_scene_set_options(opts);
 
     const int W = a.width, H = (int)cam.image_height;
@@ -174,6 +186,7 @@ int main(int argc, char** argv) {
         std::vector<rt_prim> prims(scene.size());
         for (size_t j = 0; j < scene.size(); j++) scene[j]->pack(&prims[j]);
         if (rt_set_scene(ctx, prims.data(), (int32_t)prims.size()) != RT_OK) return 1;
+        if (rt_set_option(ctx, RT_OPT_SUPERSAMPLE, a.supersample) != RT_OK) return 1;
     }
 
     std::vector<int64_t> total_times, rt_times, outpainting_times, shading_times,

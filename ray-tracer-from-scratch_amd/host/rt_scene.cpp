@@ -109,6 +109,13 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
     // several devices, or one with the loopback transport (the gather's RCCL calls on one GPU)
     const bool tiled = g.opts.devices.size() > 1 ||
                        (g.opts.devices.size() == 1 && g.opts.transport == RT_TRANSPORT_RCCL_LOOPBACK);
+    // supersampling is the one-GPU renderer's (rt_multi refuses RT_OPT_SUPERSAMPLE): refused
+    // here, before any device work
+    const int ss = g.opts.supersample;
+    if (ss != 1 && ss != 2 && ss != 4 && ss != 8)
+        throw std::invalid_argument("RtSceneOptions::supersample must be 1, 2, 4 or 8");
+    if (ss != 1 && tiled)
+        throw std::invalid_argument("RtSceneOptions::supersample > 1 needs the one-GPU renderer");
     if (tiled && (!g.multi || g.multi_devices != g.opts.devices ||
                   g.multi_transport != g.opts.transport)) {
         if (g.multi) rt_multi_destroy(g.multi);
@@ -161,10 +168,12 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
         check_multi(rt_multi_render(g.multi, &c, g.opts.depth, g.opts.precision, g.opts.flags,
                                     RT_OUT_RGB_F64, g.staging.data(), nullptr),
                     g.multi, "rt_multi_render");
-    else
+    else {
+        check(rt_set_option(g.ctx, RT_OPT_SUPERSAMPLE, ss), g.ctx, "rt_set_option");
         check(rt_render(g.ctx, &c, 0, H, g.opts.depth, g.opts.precision, g.opts.flags,
                         RT_OUT_RGB_F64, g.staging.data(), 0, nullptr),
               g.ctx, "rt_render");
+    }
     for (int i = 0; i < H; i++)
         for (int j = 0; j < W; j++) {
             const double* p = &g.staging[((size_t)i * W + j) * 3];

@@ -74,6 +74,7 @@ RT_OPT_MULTI_FAULT = 18
 RT_OPT_MULTI_BATCH = 19
 RT_OPT_MULTI_TIMEOUT_MS = 20
 RT_OPT_FRAME_BATCH = 21
+RT_OPT_SUPERSAMPLE = 22      # S in {1, 2, 4, 8}: S x S rays per pixel, mean stored (changes output)
 RT_OPT_ROW_FEEDBACK_EMA = 14
 RT_OPT_ROW_FEEDBACK_ISOLATE = 15
 
@@ -152,6 +153,7 @@ SIGNATURES = [
     ("rt_camera_init", C.c_int,
      [_dbl3, _dbl3, _dbl3, C.c_double, C.c_double, C.c_double, C.POINTER(rt_camera)]),
     ("rt_out_bytes_per_pixel", C.c_int32, [C.c_int32]),
+    ("rt_supersample_camera", C.c_int, [C.POINTER(rt_camera), C.c_int32, C.POINTER(rt_camera)]),
     ("rt_band_rows", C.c_int,
      [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("rt_max_depth", C.c_int32, []),
@@ -256,6 +258,15 @@ def camera_init(position, lookat, vup, vfov: float, aspect_ratio: float,
     check(lib.rt_camera_init(_d3(position), _d3(lookat), _d3(vup), float(vfov),
                              float(aspect_ratio), float(image_width), C.byref(cam)))
     return cam
+
+
+def supersample_camera(cam: rt_camera, s: int) -> rt_camera:
+    """rt_supersample_camera (host only): the camera of RT_OPT_SUPERSAMPLE's S-times larger
+    frame, whose pixel (j*S + a, i*S + b) is sub-sample (a, b) of cam's pixel (j, i)."""
+    lib = load()
+    out = rt_camera()
+    check(lib.rt_supersample_camera(C.byref(cam), int(s), C.byref(out)))
+    return out
 
 
 def frame_boxes(prims, cam: rt_camera, row0: int = 0, nrows: int | None = None):
