@@ -15,7 +15,12 @@ oracle/ref_harness.cpp and writes DATA only (inputs + expected outputs):
                               implicit double->Uint8 conversion, g++ -O3 x86-64) of every
                               frame in frames.npz, plus edge values (wrap above 1.0, NaN)
 
-Usage:  python tests/golden/make_golden.py [--only surface]
+  tests/golden/views.npz      tilted walls (normal.z != 0, un-normalised raw normals), rolled
+                              and z-looking cameras, non-default materials: scenes as rt_prim
+                              bytes, views as Camera::init arguments and results, frames,
+                              single rays with find_closest_hit records, Wall::intersect answers
+
+Usage:  python tests/golden/make_golden.py [--only surface|views]
 """
 from __future__ import annotations
 
@@ -60,11 +65,207 @@ def make_surface(ref) -> None:
     np.savez_compressed(os.path.join(HERE, "surface.npz"), **out)
 
 
+# ---- views.npz: tilted walls, free cameras, varied materials ---------------------------
+def _wall_at(mat, centre, raw_normal, length, width):
+    """A wall given by its CENTRE: the corner the constructor wants is centre - right*L/2 -
+    up*W/2 with the reference's basis (scene.cpp:18-19) of the normalised normal."""
+    n = np.array(scenes.normalize3(raw_normal))
+    right = np.cross(n, (0.0, 0.0, 1.0))
+    right /= np.linalg.norm(right)
+    up = np.cross(right, n)
+    up /= np.linalg.norm(up)
+    corner = np.array(centre, np.float64) - right * (length / 2) - up * (width / 2)
+    return scenes.Wall(mat, tuple(float(round(c, 6)) for c in corner), raw_normal, length, width)
+
+
+# (centre, raw normal (un-normalised on purpose), length, width, grey)
+TILT_WALLS = [
+    ((6.6, 0.2, -0.5), (-1.5, 0.3, 2.0), 5.0, 3.0, .55),      # ramp rising in +x, faces up
+    ((5.0, 2.9, 0.9), (0.2, -2.0, 0.9), 4.0, 2.5, .70),       # faces -y and up ...
+    ((5.0, -2.9, 0.9), (-0.3, 3.0, 0.9), 4.5, 2.0, .35),      # ... and its opposite number
+    ((4.0, 0.0, 2.6), (0.25, 0.1, -0.4), 3.0, 5.0, .60),      # overhead, faces down
+    ((2.6, -0.9, 0.2), (2.0, -0.5, 1.0), 1.6, 1.1, .80),      # its back to the origin
+    ((1.8, 1.6, -0.4), (-0.6, -0.45, 0.25), 1.2, 2.2, .45),   # low, near the camera
+    ((6.3, -0.8, 1.6), (0.5, -0.6, 1.5), 1.4, 0.9, .65),      # small, high up, faces up
+]
+NEAR_Z_WALL = ((5.0, 0.0, -1.35), (0.02, 0.01, -1.0), 9.0, 7.0, .50)
+CLOUD_WALLS = [
+    ((5.0, 0.3, 2.3), (0.5, -0.3, -1.2), 5.0, 3.5, .6),
+    ((5.2, -0.2, -1.2), (-0.6, 0.4, 1.7), 4.0, 6.0, .4),
+    ((7.4, 0.5, 0.4), (-2.0, 0.4, 0.9), 3.0, 2.0, .7),
+    ((3.1, -0.6, 0.6), (-1.1, -0.3, -0.5), 2.5, 1.5, .5),
+]
+
+
+def _cam(position, direction, vup, vfov, aspect, width):
+    """Rays leave along position - lookat (scene.cpp:80-106), so lookat = position - direction."""
+    look = tuple(float(p) - float(d) for p, d in zip(position, direction))
+    return dict(position=tuple(map(float, position)), lookat=look, vup=tuple(map(float, vup)),
+                vfov=float(vfov), aspect_ratio=float(aspect), image_width=float(width))
+
+
+VIEWS = {
+    "rolled": _cam((0.4, -0.3, 0.2), (1.0, 0.1, -0.05), (0.3, 0.2, -1.0), 90.0, 16 / 9, 48),
+    "up": _cam((5.4, 0.1, -1.25), (0.0, 0.0, 1.0), (0.0, -1.0, 0.0), 90.0, 1.0, 32),
+    "down": _cam((6.3, 0.6, 3.0), (0.0, 0.0, -1.0), (1.0, 0.0, 0.0), 90.0, 4 / 3, 37),
+    "wide": _cam((1.0, 1.0, 0.5), (1.0, -0.25, 0.0), (0.0, 0.0, -1.0), 150.0, 0.5, 24),
+    "narrow": None,   # filled in by views_scenes(): aimed at a corner of the back-facing wall
+    "inside": None,   # likewise: a point inside tilt's first sphere
+    "cloud_a": _cam((5.0, 0.2, 0.5), (1.0, 0.3, 0.2), (0.3, 0.2, -1.0), 100.0, 4 / 3, 40),
+    "cloud_b": _cam((4.6, -0.4, 0.3), (0.1, 0.2, 1.0), (0.0, -1.0, 0.0), 110.0, 1.0, 31),
+}
+VIEW_FRAMES = ([("tilt", v, 5) for v in ("rolled", "up", "down", "wide", "narrow", "inside")] +
+               [("tilt", "rolled", 0)] +
+               [(s, v, 5) for s in ("tilt_mat", "tilt_wild") for v in ("rolled", "down")] +
+               [("cloud", "cloud_a", 5), ("cloud", "cloud_b", 5)])
+
+
+def views_scenes():
+    """The four scenes of views.npz (seeded, fixed) -> {name: scene}."""
+    M = scenes.Material
+    tilt = scenes.synthetic_scene(6, 3, seed=4242)
+    for c, n, ln, wd, g in TILT_WALLS + [NEAR_Z_WALL]:
+        tilt.append(_wall_at(M((g, g * .9, g * .8), .5), c, n, ln, wd))
+    c, n, ln, wd, _ = TILT_WALLS[4]
+    corner = _wall_at(None, c, n, -ln, -wd).position     # the corner opposite the wall's own
+    eye = (0.2, 0.4, 0.6)
+    VIEWS["narrow"] = _cam(eye, tuple(round(a - b, 3) for a, b in zip(corner, eye)),
+                           (0.0, 0.0, -1.0), 5.0, 4 / 3, 40)
+    s0 = tilt[0]
+    VIEWS["inside"] = _cam(tuple(p + .1 * s0.radius for p in s0.position), (-1.0, 0.2, 0.1),
+                           (0.1, 0.0, -1.0), 90.0, 4 / 3, 32)
+
+    def remat(pick):
+        out = []
+        for o in tilt:
+            q = scenes.SceneObject(o.kind, pick(), o.position, o.normal, o.radius, o.length, o.width)
+            out.append(q)
+        return out
+
+    rng = np.random.default_rng(20261020)
+    turn = iter(range(10 ** 6))     # metallic goes round its set, so every value occurs
+
+    def bounded():
+        while True:
+            a, d, s = rng.choice([0, .1, .3]), rng.choice([0, .5, .9]), rng.choice([0, .4, 1])
+            if a + d + s <= 1.4 + 1e-12:
+                break
+        col = tuple(float(c) for c in rng.choice([0.0, 0.25, 0.6, 1.0], size=3))
+        return M(col, [0.0, .25, .9, 1.0][next(turn) % 4], float(a), float(d), float(s),
+                 float(rng.choice([1, 2, 7, 50, 200])))
+
+    def wild():
+        col = [float(c) for c in rng.choice([0.0, 0.3, 0.8, 1.0], size=3)]
+        if rng.random() < .35:
+            col[int(rng.integers(3))] = 2.0
+        return M(tuple(col), [0.0, 1.0, 1.5, -0.25][next(turn) % 4],
+                 float(rng.choice([-0.1, .1, .3])), float(rng.choice([0, .5, .9])),
+                 float(rng.choice([0, .4, 2.0])), float(rng.choice([0, 1024, 1025, 0.5, 37.5])))
+
+    cloud = scenes.synthetic_scene(64, 6)
+    for c, n, ln, wd, g in CLOUD_WALLS:
+        cloud.append(_wall_at(M((g, g, g * .7), .5), c, n, ln, wd))
+    return {"tilt": tilt, "tilt_mat": remat(bounded), "tilt_wild": remat(wild), "cloud": cloud}
+
+
+def make_views(ref) -> None:
+    """views.npz: scenes as rt_prim bytes + raw normals, views as camera_init arguments + the
+    reference's Camera::init, the reference's frames, single rays with hit records, and
+    Wall::intersect known answers on tilted, un-normalised normals.  Data only."""
+    import ctypes as C
+    L, A = ref.lib, orc_mod._arr
+    out = {}
+    scs = views_scenes()
+    out["scene_names"] = np.array(list(scs))
+    packed = {}
+    for name, sc in scs.items():
+        prims, raw = scenes.to_prims(sc), scenes.raw_normals(sc)
+        packed[name] = (prims, raw)
+        arr = orc_mod.Oracle.prim_array(prims)
+        out[f"{name}__prims"] = np.frombuffer(bytes(arr), np.uint8).copy()
+        out[f"{name}__raw"] = np.array(raw, np.float64).reshape(-1, 3)
+    out["view_names"] = np.array(list(VIEWS))
+    for vname, ca in VIEWS.items():
+        out[f"{vname}__args"] = np.array(list(ca["position"]) + list(ca["lookat"]) + list(ca["vup"]) +
+                                         [ca["vfov"], ca["aspect_ratio"], ca["image_width"]])
+        h, v = ref.camera_init(**ca)
+        out[f"{vname}__refcam"] = v.reshape(-1)
+        out[f"{vname}__height"] = np.int32(h)
+    for sname, vname, depth in VIEW_FRAMES:
+        prims, raw = packed[sname]
+        out[f"frame__{sname}__{vname}__d{depth}"] = ref.render(prims, raw, VIEWS[vname], depth)
+    rng = np.random.default_rng(20261021)
+    for sname, (prims, raw) in packed.items():
+        n = 300
+        o = rng.uniform([-2, -5, -2], [9, 5, 3], size=(n, 3))
+        d = rng.normal(size=(n, 3)) * rng.choice([0.3, 1.0, 2.0], size=(n, 1))
+        depth = rng.integers(0, 9, size=n).astype(np.int8)
+        rgb, idx, dist, nrm = np.empty((n, 3)), np.empty(n, np.int32), np.empty(n), np.empty((n, 3))
+        arr, rawa = orc_mod.Oracle.prim_array(prims), A(raw, len(raw))
+        for k in range(n):
+            out3, dk, nk = (C.c_double * 3)(), C.c_double(), (C.c_double * 3)()
+            L.ref_trace(arr, rawa, len(prims), A(o[k]), A(d[k]), int(depth[k]), out3)
+            rgb[k] = list(out3)
+            idx[k] = L.ref_find_closest_hit(arr, rawa, len(prims), A(o[k]), A(d[k]), C.byref(dk), nk)
+            dist[k], nrm[k] = dk.value, list(nk)
+        for key, v in (("o", o), ("d", d), ("depth", depth), ("rgb", rgb), ("hit_index", idx),
+                       ("hit_dist", dist), ("hit_normal", nrm)):
+            out[f"{sname}__ray_{key}"] = v
+    # Wall::intersect on tilted, un-normalised normals.  Targets are given in the wall's own
+    # (px, py) coordinates; the ray runs from o through P + px*right + py*up.
+    cases = []
+    walls = [(p, n, ln, wd) for p, n, ln, wd in
+             [((2.0, -1.0, 0.5), (-1.5, 0.3, 2.0), 3.0, 2.0), ((4.0, 1.0, -0.5), (0.6, -3.0, 1.2), 2.5, 1.5)]]
+    eps = 1e-6
+    for wi, (p, nraw, ln, wd) in enumerate(walls):
+        n = np.array(scenes.normalize3(nraw))
+        right = np.cross(n, (0.0, 0.0, 1.0))
+        right /= np.linalg.norm(right)
+        up = np.cross(right, n)
+        up /= np.linalg.norm(up)
+        front = np.array(p) + right * ln / 2 + up * wd / 2 + n * 2.0 + np.array([.3, -.2, .1])
+        back = np.array(p) + right * ln / 2 + up * wd / 2 - n * 1.5 + np.array([-.2, .1, .3])
+        targets = [("front", front, ln * .4, wd * .6), ("back_side", back, ln * .7, wd * .3),
+                   ("in_px0", front, eps, wd * .5), ("in_px1", front, ln - eps, wd * .5),
+                   ("in_py0", front, ln * .5, eps), ("in_py1", front, ln * .5, wd - eps),
+                   ("out_px0", front, -eps, wd * .5), ("out_px1", front, ln + eps, wd * .5),
+                   ("out_py0", front, ln * .5, -eps), ("out_py1", front, ln * .5, wd + eps)]
+        for name, o, px, py in targets:
+            tgt = np.array(p) + right * px + up * py
+            cases.append((f"w{wi}_{name}", p, nraw, ln, wd, o, (tgt - o) * 0.8))
+        cases.append((f"w{wi}_parallel", p, nraw, ln, wd, front, right * 1.3 + up * 0.4))
+        cases.append((f"w{wi}_behind_origin", p, nraw, ln, wd, front, front - (np.array(p) + right + up)))
+    nzp, nzn = (1.0, -2.0, -1.0), (0.02, 0.01, -1.0)
+    cases.append(("near_z_from_above", nzp, nzn, 4.0, 3.0, (2.0, -1.0, 2.0), (0.3, -0.4, -1.0)))
+    cases.append(("near_z_from_below", nzp, nzn, 4.0, 3.0, (2.5, -2.5, -3.0), (-0.1, 0.2, 1.0)))
+    cases.append(("near_z_outside", nzp, nzn, 4.0, 3.0, (2.0, -1.0, 2.0), (3.0, 3.0, -1.0)))
+    k = len(cases)
+    out["wallkat__name"] = np.array([c[0] for c in cases])
+    for j, key in ((1, "position"), (2, "raw_normal"), (5, "o"), (6, "d")):
+        out[f"wallkat__{key}"] = np.array([np.asarray(c[j], np.float64) for c in cases])
+    out["wallkat__length"] = np.array([c[3] for c in cases], np.float64)
+    out["wallkat__width"] = np.array([c[4] for c in cases], np.float64)
+    dist, nrm, hit = np.empty(k), np.empty((k, 3)), np.empty(k, np.int32)
+    for j, (_, p, nraw, ln, wd, o, d) in enumerate(cases):
+        dk, nk, hk = C.c_double(), (C.c_double * 3)(), C.c_int()
+        L.ref_wall_intersect(A(p), A(nraw), ln, wd, A(o), A(d), C.byref(dk), nk, C.byref(hk))
+        dist[j], nrm[j], hit[j] = dk.value, list(nk), hk.value
+    out["wallkat__dist"], out["wallkat__normal"], out["wallkat__hit"] = dist, nrm, hit
+    path = os.path.join(HERE, "views.npz")
+    np.savez_compressed(path, **out)
+    print("wrote views.npz:", os.path.getsize(path), "bytes,", len(VIEW_FRAMES), "frames,", k,
+          "wall cases")
+
+
 def main() -> None:
     orc_mod.build(ref=True)
     ref = orc_mod.Reference()
-    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "surface":
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+    if only == "surface":
         make_surface(ref)
+        return
+    if only == "views":
+        make_views(ref)
         return
     L = ref.lib
     A = orc_mod._arr
@@ -203,6 +404,7 @@ def main() -> None:
         rays[f"{scene_name}__rgb"] = rgb
     np.savez_compressed(os.path.join(HERE, "rays.npz"), **rays)
     make_surface(ref)
+    make_views(ref)
     print("wrote", sorted(os.listdir(HERE)))
 
 

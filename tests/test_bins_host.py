@@ -6,82 +6,16 @@ in w; likewise for two-wall chains.  The kernel skips a primitive for an 8x8 til
 when its box misses the whole tile, so this is the property the GPU path's exactness
 rests on (the GPU test test_tile_bins_are_output_invariant checks the frames themselves).
 No device is used."""
-import math
-
 import numpy as np
 import pytest
 
 from rtamd import capi, scenes
 
-B = 1000003  # rt_oracle.c path signature: sig = sig * B + (scene index + 1) per segment
-
-
-def _slots(sc):
-    """scene index -> material slot (spheres in order, then walls that can ever be hit)."""
-    sph = [j for j, o in enumerate(sc) if o.kind == capi.RT_PRIM_SPHERE]
-    wal = []
-    for j, o in enumerate(sc):
-        if o.kind != capi.RT_PRIM_WALL:
-            continue
-        n = scenes.normalize3(o.normal)
-        cz = (n[1], -n[0], 0.0)  # cross(n, z)
-        if math.isnan(n[0]) or (cz[0] == 0.0 and cz[1] == 0.0):
-            continue  # NaN basis: never hit, not uploaded
-        wal.append(j)
-    m = {j: s for s, j in enumerate(sph)}
-    m.update({j: len(sph) + w for w, j in enumerate(wal)})
-    return m, len(sph), len(wal)
-
-
-def _decode(sig):
-    """path signature -> list of scene indices (-1 = miss) per segment (<= 3 segments)."""
-    sig = int(sig)
-    digits = []
-    while True:
-        digits.append(sig % B)
-        sig //= B
-        if sig == 0:
-            break
-    return [d - 1 for d in reversed(digits)]
-
-
-def _inside(box, x, i):
-    return box[0] <= x <= box[1] and box[2] <= i <= box[3]
+from boxes_check import check_boxes
 
 
 def _check(oracle, sc, cam, row0=0, nrows=None):
-    prims = scenes.to_prims(sc)
-    if nrows is None:
-        nrows = cam.height - row0
-    prim_boxes, mir, depth = capi.frame_boxes(prims, cam, row0, nrows)
-    slot, nS, nW = _slots(sc)
-    np_ = nS + nW
-    assert len(prim_boxes) == np_
-    _, _, _, sig = oracle.render(prims, cam, 2, row0=row0, nrows=nrows, want64=False,
-                                 want_sig=True)
-    lvl1 = mir[:nW * np_].reshape(nW, np_, 4) if depth >= 1 else None
-    lvl2 = mir[nW * np_:nW * np_ + nW * nW * np_].reshape(nW, nW, np_, 4) if depth >= 2 else None
-    checked = [0, 0, 0]
-    for r in range(nrows):
-        i = row0 + r
-        for x in range(cam.width):
-            path = _decode(sig[r, x])
-            if path[0] < 0:
-                continue
-            s0 = slot[path[0]]
-            assert _inside(prim_boxes[s0], x, i), ("primary", x, i, s0, prim_boxes[s0])
-            checked[0] += 1
-            if len(path) < 2 or path[1] < 0 or s0 < nS or lvl1 is None:
-                continue
-            w1, s1 = s0 - nS, slot[path[1]]
-            assert _inside(lvl1[w1, s1], x, i), ("bounce 1", x, i, w1, s1, lvl1[w1, s1])
-            checked[1] += 1
-            if len(path) < 3 or path[2] < 0 or s1 < nS or lvl2 is None:
-                continue
-            w2, s2 = s1 - nS, slot[path[2]]
-            assert _inside(lvl2[w1, w2, s2], x, i), ("bounce 2", x, i, w1, w2, s2)
-            checked[2] += 1
-    return prim_boxes, checked
+    return check_boxes(oracle, scenes.to_prims(sc), cam, row0, nrows)
 
 
 def test_boxes_cover_every_primary_and_mirror_hit_config_scenes(oracle):
