@@ -179,6 +179,16 @@ std::vector<Collision> rt_closest_hits(const std::vector<std::unique_ptr<SceneGe
                                        const std::vector<ray>& rays);
 std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
                              const std::vector<ray>& rays, int remaining_iterations = 10);
+/* The occlusion query (rt_occluded, include/rt_capi.h) over the same renderer:
+ *   rt_occluded()[k] == 1 iff some scene[j]->intersect(rays[k]) has distance > 0 and its
+ *   parameter along the ray (a wall's distance; a sphere's distance before the * |d|) is
+ *   <= tmax[k].
+ * tmax is empty (+inf for every ray) or holds one limit per ray (any other size throws
+ * std::invalid_argument).  A SceneGeometry subclass without a GPU record throws
+ * std::invalid_argument, as above. */
+std::vector<unsigned char> rt_occluded(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                                       const std::vector<ray>& rays,
+                                       const std::vector<double>& tmax = {});
 /* One rt_hit record (rt_trace_rays through the C-ABI directly) as the reference's Collision. */
 Collision rt_collision_from_hit(const rt_hit& h);
 

@@ -32,7 +32,8 @@ extern "C" {
 
 /* Version 2 adds the multi-GPU frame operator (rt_multi_*) and RT_ERR_COMM; every version-1
  * entry point keeps its signature and meaning (the ABI grows additively).  The ray queries
- * (rt_hit, rt_trace_rays, rt_trace_rays_device) arrived within version 2: purely additive. */
+ * (rt_hit, rt_trace_rays, rt_trace_rays_device, then rt_occluded, rt_occluded_device) arrived
+ * within version 2: purely additive. */
 #define RT_CAPI_VERSION 2
 
 /* ---- status codes ------------------------------------------------------- */
@@ -319,7 +320,7 @@ enum rt_option {
                                          rt_render_device_interleaved with nparts > 1 returns
                                          RT_ERR_UNSUPPORTED while S > 1, and
                                          rt_multi_set_option refuses S != 1 with
-                                         RT_ERR_UNSUPPORTED.  rt_trace_rays*,
+                                         RT_ERR_UNSUPPORTED.  rt_trace_rays*, rt_occluded*,
                                          rt_tile_row_costs and rt_frame_boxes ignore it. */
     RT_OPT_CLUSTER_COS = 12          /* C in [-2000, 2000] (default 400): in scenes that use
                                          the wave cull, a wave (any precision) whose live
@@ -416,6 +417,46 @@ int rt_trace_rays(rt_ctx* ctx, const double* origins, const double* directions, 
 int rt_trace_rays_device(rt_ctx* ctx, const double* d_origins, const double* d_directions, int64_t n,
                          int32_t depth, int32_t precision, uint32_t flags, int32_t out_format,
                          void* d_out, rt_hit* d_hits, uint64_t* d_segments, void* stream);
+
+/* ---- occlusion queries (any hit on a segment) ---------------------------------------- */
+/* Is anything on the segment from o to o + d * tmax?  The visibility / line-of-sight probe:
+ * it stops at the first blocker, discards everything beyond tmax and returns one byte per ray.
+ * (An rt_hit cannot answer it for |d| != 1: find_closest_hit ranks a sphere's world distance
+ * against a wall's parametric t — the reference's quirk, kept there — so its record need not
+ * be the first thing along the ray.)
+ *
+ * For ray k (origin o, direction d — NOT normalised; finite and non-zero as for rt_trace_rays —
+ * and limit T = tmax[k]), occluded[k] = 1 iff some scene object j has, with the reference's
+ * c = scene[j]->intersect(ray(d, o)),
+ *   1. c.distance > 0 — find_closest_hit's own acceptance test (main.cpp:77), so a ray that
+ *      starts inside a sphere is not blocked by that sphere, as in the reference; and
+ *   2. param(c) <= T, where param is the hit's PARAMETER along the ray: a wall's c.distance
+ *      (its t, scene.cpp:10); a sphere's `projection`, the value scene.cpp:77 multiplies by
+ *      |d| to form c.distance.
+ * Otherwise 0.  The comparison is the fp64 <= on those exact values (there is no precision
+ * argument: the answer is exact); a NaN T and T <= 0 are never occluded; tmax == NULL means
+ * +inf for every ray; an empty scene gives all zeros.  Hence, with tmax == NULL,
+ * occluded[k] == (hits[k].index >= 0) for rt_trace_rays' record of the same ray, and with T
+ * equal to the smallest param over the blockers the ray is occluded while the next double
+ * towards 0 is not.  Between two points a and b: d = b - a, tmax = 1 (slightly less when b
+ * itself lies on a surface).
+ *
+ * out: n bytes (1 = occluded, 0 = free); count: the number of occluded rays.  Either may be
+ * NULL, not both (RT_ERR_INVALID_ARG).  n == 0: RT_OK, nothing launched, outputs untouched;
+ * n < 0 or n > INT32_MAX: RT_ERR_INVALID_ARG; RT_ERR_NO_SCENE before rt_set_scene.
+ * RT_OPT_WAVE_CULL_MIN_SPHERES and RT_OPT_CLUSTER_COS apply as for ray batches; the frame-only
+ * options (RT_OPT_SUPERSAMPLE included) are ignored and their cached state is left as it was.
+ *
+ * rt_occluded: host memory in and out, synchronous (staging buffers in the ctx); stats->ms =
+ * device time of the kernel, stats->segments = n. */
+int rt_occluded(rt_ctx* ctx, const double* origins, const double* directions, const double* tmax,
+                int64_t n, uint8_t* out, uint64_t* count, rt_stats* stats);
+/* The same with every buffer in DEVICE memory, enqueued on `stream` (NULL = the ctx's) without
+ * synchronising; *d_count += the occluded rays.  The launch signals the ctx's per-stream event
+ * that rt_set_scene and rt_ctx_destroy wait on. */
+int rt_occluded_device(rt_ctx* ctx, const double* d_origins, const double* d_directions,
+                       const double* d_tmax, int64_t n, uint8_t* d_out, uint64_t* d_count,
+                       void* stream);
 
 /* ---- multi-GPU frame operator (BASELINE config 4) ----------------------- */
 /* ONE frame split into contiguous row bands (rt_band_rows) over nranks ranks, one GPU each,

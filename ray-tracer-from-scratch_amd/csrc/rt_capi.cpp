@@ -164,7 +164,8 @@ struct rt_ctx {
     void* d_out = nullptr;
     size_t d_out_cap = 0;
     unsigned long long* d_segs = nullptr;
-    // rt_trace_rays' staging buffers: origins then directions; hit records (d_out: colours)
+    // rt_trace_rays' staging buffers: origins then directions; hit records (d_out: colours).
+    // rt_occluded's too: origins, directions, limits; the mask bytes in d_hits
     void* d_rays = nullptr;
     size_t d_rays_cap = 0;
     void* d_hits = nullptr;
@@ -2141,6 +2142,104 @@ int rt_trace_rays(rt_ctx* ctx, const double* origins, const double* directions, 
         RT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         stats->ms = ms;
         stats->segments = hsegs;
+    }
+    return RT_OK;
+}
+
+}  // extern "C"
+
+/* ---- occlusion queries (rt_occluded*) ---------------------------------------------------
+ * rt_rays.hip k_ray_occluded.  As for ray batches nothing of a frame takes part, and the
+ * frame-only options (RT_OPT_SUPERSAMPLE among them) and their cached state are untouched. */
+namespace {
+
+int check_occluded_args(const rt_ctx* ctx, const double* origins, const double* directions,
+                        int64_t n, const void* out, const void* count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (n < 0 || n > INT32_MAX) return RT_ERR_INVALID_ARG;
+    if (!out && !count) return RT_ERR_INVALID_ARG;
+    if (n > 0 && (!origins || !directions)) return RT_ERR_INVALID_ARG;
+    if (!ctx->have_scene) return RT_ERR_NO_SCENE;
+    return RT_OK;
+}
+
+int launch_occluded_batch(rt_ctx* ctx, const double* d_origins, const double* d_directions,
+                          const double* d_tmax, int64_t n, uint8_t* d_out,
+                          unsigned long long* d_count, hipStream_t hs, hipEvent_t done) {
+    rt::KParams p{};
+    scene_params(ctx, RT_PREC_F64, p);  // the fp64 kernels' cluster set
+    rt::OccArgs oa{};
+    oa.org = d_origins;
+    oa.dir = d_directions;
+    oa.tmax = d_tmax;
+    oa.out = d_out;
+    oa.count = d_count;
+    oa.n = (int32_t)n;
+    const int e = rt::launch_occluded(p, oa, hs, done);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_ray_occluded");
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_occluded_device(rt_ctx* ctx, const double* d_origins, const double* d_directions,
+                       const double* d_tmax, int64_t n, uint8_t* d_out, uint64_t* d_count,
+                       void* stream) {
+    int st = check_occluded_args(ctx, d_origins, d_directions, n, d_out, d_count);
+    if (st != RT_OK || n == 0) return st;
+    DeviceGuard dg(ctx->device);
+    RT_HIP(ctx, dg.err);
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    hipEvent_t done = nullptr;
+    st = launch_event(ctx, hs, &done);
+    if (st != RT_OK) return st;
+    return launch_occluded_batch(ctx, d_origins, d_directions, d_tmax, n, d_out,
+                                 reinterpret_cast<unsigned long long*>(d_count), hs, done);
+}
+
+int rt_occluded(rt_ctx* ctx, const double* origins, const double* directions, const double* tmax,
+                int64_t n, uint8_t* out, uint64_t* count, rt_stats* stats) {
+    int st = check_occluded_args(ctx, origins, directions, n, out, count);
+    if (st != RT_OK) return st;
+    if (n == 0) {
+        if (stats) {
+            stats->ms = 0.0;
+            stats->segments = 0;
+        }
+        return RT_OK;
+    }
+    DeviceGuard dg(ctx->device);
+    RT_HIP(ctx, dg.err);
+    const size_t in_bytes = (size_t)n * 3 * sizeof(double);
+    const size_t t_bytes = tmax ? (size_t)n * sizeof(double) : 0;
+    if ((st = grow(ctx, &ctx->d_rays, &ctx->d_rays_cap, 2 * in_bytes + t_bytes)) != RT_OK) return st;
+    if ((st = grow(ctx, &ctx->d_hits, &ctx->d_hits_cap, out ? (size_t)n : 0)) != RT_OK) return st;
+    double* d_o = static_cast<double*>(ctx->d_rays);
+    double* d_d = d_o + (size_t)n * 3;
+    double* d_t = tmax ? d_d + (size_t)n * 3 : nullptr;
+    RT_HIP(ctx, hipMemcpyAsync(d_o, origins, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(d_d, directions, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (tmax) RT_HIP(ctx, hipMemcpyAsync(d_t, tmax, t_bytes, hipMemcpyHostToDevice, ctx->stream));
+    unsigned long long* d_cnt = count ? ctx->d_segs : nullptr;
+    if (d_cnt) RT_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof *d_cnt, ctx->stream));
+    RT_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    st = launch_occluded_batch(ctx, d_o, d_d, d_t, n, out ? static_cast<uint8_t*>(ctx->d_hits) : nullptr,
+                               d_cnt, ctx->stream, nullptr);
+    if (st != RT_OK) return st;
+    RT_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    if (out) RT_HIP(ctx, hipMemcpyAsync(out, ctx->d_hits, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned long long hcnt = 0;
+    if (d_cnt)
+        RT_HIP(ctx, hipMemcpyAsync(&hcnt, d_cnt, sizeof hcnt, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (count) *count = hcnt;
+    if (stats) {
+        float ms = 0.f;
+        RT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        stats->ms = ms;
+        stats->segments = (uint64_t)n;
     }
     return RT_OK;
 }

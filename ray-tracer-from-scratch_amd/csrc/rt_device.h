@@ -255,6 +255,18 @@ struct RayArgs {
 // prec: PREC_F64 or PREC_PATH64 (anything else: hipErrorInvalidValue)
 int launch_rays(const KParams& p, const RayArgs& ra, int prec, void* stream, void* done_event);
 
+// Occlusion queries (rt_occluded*, rt_rays.hip k_ray_occluded): is anything on the segment
+// o .. o + d * tmax of each caller ray?  Only the scene and cull fields of KParams are used.
+struct OccArgs {
+    const double* org;   // [n][3]
+    const double* dir;   // [n][3], not normalised
+    const double* tmax;  // [n] parametric limit of each ray, null = +inf for every ray
+    uint8_t* out;        // [n] 1 = occluded, 0 = free; may be null
+    unsigned long long* count;  // += occluded rays (one atomic per wave); may be null
+    int32_t n;
+};
+int launch_occluded(const KParams& p, const OccArgs& oa, void* stream, void* done_event);
+
 // Device self-test of the exact fp64 helpers against IEEE operations:
 // which 0 = division (shared reciprocal), 1 = integer-exponent pow vs pow(),
 // 2 = sqrt_e vs sqrt(); adds the number of mismatches (division, sqrt: bitwise;

@@ -246,6 +246,24 @@ std::vector<Collision> rt_closest_hits(const std::vector<std::unique_ptr<SceneGe
     return out;
 }
 
+std::vector<unsigned char> rt_occluded(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                                       const std::vector<ray>& rays,
+                                       const std::vector<double>& tmax) {
+    if (!tmax.empty() && tmax.size() != rays.size())
+        throw std::invalid_argument("rt_occluded: tmax holds neither 0 nor one limit per ray");
+    Global& g = global();
+    std::lock_guard<std::mutex> lk(g.mu);
+    ray_scene(g, scene);
+    std::vector<double> o, d;
+    flatten_rays(rays, o, d);
+    std::vector<unsigned char> out(rays.size());
+    if (rays.empty()) return out;
+    check(rt_occluded(g.ctx, o.data(), d.data(), tmax.empty() ? nullptr : tmax.data(),
+                      (int64_t)rays.size(), out.data(), nullptr, nullptr),
+          g.ctx, "rt_occluded");
+    return out;
+}
+
 std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
                              const std::vector<ray>& rays, int remaining_iterations) {
     Global& g = global();

@@ -175,6 +175,12 @@ SIGNATURES = [
     ("rt_trace_rays_device", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_int32,
       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_occluded", C.c_int,
+     [C.c_void_p, _dbl3, _dbl3, _dbl3, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64),
+      C.POINTER(rt_stats)]),
+    ("rt_occluded_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+      C.c_void_p]),
     # multi-GPU frame operator
     ("rt_multi_unique_id", C.c_int, [C.POINTER(C.c_uint8)]),
     ("rt_multi_create", C.c_int,
@@ -485,6 +491,36 @@ class Renderer:
             self.ctx, C.c_void_p(d_origins or None), C.c_void_p(d_directions or None), n, depth,
             precision, flags, out_format, C.c_void_p(d_out or None), C.c_void_p(d_hits or None),
             C.c_void_p(d_segments or None), C.c_void_p(stream or None)), self.ctx)
+
+    def occluded(self, origins, directions, tmax=None, want_mask: bool = True):
+        """rt_occluded: is anything on the segment o .. o + d * tmax of each ray ([n, 3] origins
+        and un-normalised directions; tmax a scalar, [n] or None = +inf), synchronous ->
+        (mask uint8[n] or None, count of occluded rays, stats)."""
+        o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float64).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("origins and directions differ in shape")
+        n = o.shape[0]
+        t = None
+        if tmax is not None:
+            t = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float64), (n,)))
+        mask = np.empty(n, np.uint8) if want_mask else None
+        count, st = C.c_uint64(), rt_stats()
+        check(self.lib.rt_occluded(
+            self.ctx, o.ctypes.data_as(_dbl3), d.ctypes.data_as(_dbl3),
+            t.ctypes.data_as(_dbl3) if t is not None else None, n,
+            mask.ctypes.data_as(C.POINTER(C.c_uint8)) if want_mask else None, C.byref(count),
+            C.byref(st)), self.ctx)
+        return mask, int(count.value), st
+
+    def occluded_device(self, d_origins: int, d_directions: int, d_tmax: int, n: int, d_out: int,
+                        d_count: int = 0, stream: int = 0) -> None:
+        """rt_occluded_device: the same on raw device addresses, enqueued on `stream` without
+        synchronising (d_tmax 0 = +inf; d_out or d_count may be 0, not both; *d_count +=)."""
+        check(self.lib.rt_occluded_device(
+            self.ctx, C.c_void_p(d_origins or None), C.c_void_p(d_directions or None),
+            C.c_void_p(d_tmax or None), n, C.c_void_p(d_out or None), C.c_void_p(d_count or None),
+            C.c_void_p(stream or None)), self.ctx)
 
 
 def multi_unique_id() -> bytes:

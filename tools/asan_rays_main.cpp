@@ -3,8 +3,8 @@
 // sanitized objects of `make asan` and the C++ mirror, and runs it; CPU only, no preloaded
 // runtime).  It packs scenes through the host-only rt_frame_boxes (pack_scene: spheres,
 // walls, an interleaved order, a wall with a NaN basis), walks the argument checks of
-// rt_trace_rays and rt_trace_rays_device, and converts hit records to Collisions.  Where a
-// HIP device exists it also runs both entry points on a small batch; without one
+// rt_trace_rays, rt_trace_rays_device and rt_occluded*, and converts hit records to
+// Collisions.  Where a HIP device exists it also runs the entry points on a small batch; without one
 // rt_ctx_create returns RT_ERR_NO_DEVICE and the device part is skipped (and said so).
 #include <cfloat>
 #include <cstdio>
@@ -74,6 +74,12 @@ int main() {
            RT_ERR_INVALID_ARG);
     EXPECT(rt_trace_rays_device(nullptr, o, d, 2, 4, RT_PREC_F64, 0, RT_OUT_RGB_F64, rgb, hits, nullptr,
                                 nullptr) == RT_ERR_INVALID_ARG);
+    uint8_t occ[2] = {7, 7};
+    uint64_t nocc = 9;
+    const double tmax[2] = {1.0, 0.5};
+    EXPECT(rt_occluded(nullptr, o, d, tmax, 2, occ, &nocc, &st) == RT_ERR_INVALID_ARG);
+    EXPECT(rt_occluded_device(nullptr, o, d, tmax, 2, occ, &nocc, nullptr) == RT_ERR_INVALID_ARG);
+    EXPECT(occ[0] == 7 && occ[1] == 7 && nocc == 9);
 
     // hit records -> Collision
     rt_hit h{};
@@ -110,6 +116,13 @@ int main() {
             EXPECT(rt_trace_rays(ctx, o, d, 0, 4, RT_PREC_F64, 0, RT_OUT_RGB_F64, rgb, hits, 1, &st) == RT_OK);
             EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, 0, RT_OUT_RGB_F64, rgb, hits, 1, &st) == RT_OK);
             EXPECT(hits[0].index == 1 && st.segments >= 2);
+            EXPECT(rt_occluded(ctx, o, d, tmax, 2, nullptr, nullptr, &st) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_occluded(ctx, o, d, tmax, -1, occ, &nocc, &st) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_occluded(ctx, o, d, tmax, 0, occ, &nocc, &st) == RT_OK && nocc == 9);
+            // ray 0 meets the sphere at parameter 1 (x = 1.5, r = .5): on the limit, blocked
+            EXPECT(rt_occluded(ctx, o, d, tmax, 2, occ, &nocc, &st) == RT_OK);
+            EXPECT(occ[0] == 1 && nocc == (uint64_t)(occ[0] + occ[1]) && st.segments == 2);
+            EXPECT(rt_occluded(ctx, o, d, nullptr, 2, occ, nullptr, nullptr) == RT_OK && occ[0] == 1);
             rt_ctx_destroy(ctx);
         }
     }
@@ -122,6 +135,13 @@ int main() {
     bool threw = false;
     try {
         rt_closest_hits(scene, {ray(vec3(1, 0, 0), point3(0, 0, 0))});
+    } catch (const std::invalid_argument&) {
+        threw = true;
+    }
+    EXPECT(threw);
+    threw = false;
+    try {
+        rt_occluded(scene, {ray(vec3(1, 0, 0), point3(0, 0, 0))}, {1.0});
     } catch (const std::invalid_argument&) {
         threw = true;
     }

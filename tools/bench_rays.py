@@ -18,6 +18,10 @@ libclock_probe.so has been built.
               algorithmic work without the frame-only shortcuts.  ratio = frame / rays time.
   random_cN   --rays uniformly random rays (the distribution of tests/golden/rays.npz,
               seeded) on config cN's scene at its depth, PATH64 and F64.
+  occluded_cN (--occluded: c2, c3, c5) the occlusion query (rt_occluded_device) and the
+              closest-hit-only query (rt_trace_rays_device without radiance) on the same
+              --rays random rays and scene, tmax = inf; then on random point pairs (d = b - a)
+              with tmax = 1 and inf.  ns per ray of each.
 
 The last line printed is one JSON object {"steps": [...]}; --out also writes it to a file.
 """
@@ -34,6 +38,7 @@ sys.path.insert(0, os.path.join(REPO, "ray-tracer-from-scratch_amd"))
 
 STEP_LIMIT_S = 240
 ALL_STEPS = "camera_c2,random_c2,random_c3,random_c5"
+OCCLUDED_STEPS = "occluded_c2,occluded_c3,occluded_c5"
 
 
 def camera_rays(cam):
@@ -150,9 +155,92 @@ def run_step(step, args):
     print(json.dumps(res), flush=True)
 
 
+def run_occluded_step(step, args):
+    """occluded_cN: the occlusion query against the closest-hit-only query (want_rgb=False:
+    hit records, no shading) on the same rays and scene in one process.  Random rays with
+    tmax = inf for both, then random point pairs in the same box (d = b - a) with tmax = 1 for
+    the occlusion query — closest-hit has no limit to give."""
+    import numpy as np
+    import torch
+    from rtamd import capi, scenes
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(dev)
+    cname = step.split("_")[1]
+    cfg = scenes.CONFIGS[cname]
+    rend = capi.Renderer(0)
+    rend.set_scene(scenes.to_prims(cfg.scene()))
+    n = args.rays
+    o, d = random_rays(n)
+    rng = np.random.default_rng(20261020)
+    b = rng.uniform([-2, -5, -2], [9, 5, 3], size=(n, 3))
+    sp = stream.cuda_stream
+    t_o = torch.from_numpy(o).to(dev)
+    t_d = torch.from_numpy(d).to(dev)
+    t_pd = torch.from_numpy(b - o).to(dev)
+    t_one = torch.ones(n, dtype=torch.float64, device=dev)
+    mask = torch.zeros(n, dtype=torch.uint8, device=dev)
+    hits = torch.zeros(n * 40, dtype=torch.uint8, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def occ(dirs, tmax):
+        return lambda c=0: rend.occluded_device(t_o.data_ptr(), dirs.data_ptr(), tmax, n,
+                                                mask.data_ptr(), c, sp)
+
+    def closest(dirs):
+        return lambda c=0: rend.trace_rays_device(t_o.data_ptr(), dirs.data_ptr(), n, 0, 0,
+                                                  hits.data_ptr(), stream=sp)
+
+    variants = [("occluded", "random", "inf", occ(t_d, 0)),
+                ("closest_hit", "random", "-", closest(t_d)),
+                ("occluded", "point_pairs", "1", occ(t_pd, t_one.data_ptr())),
+                ("occluded", "point_pairs", "inf", occ(t_pd, 0)),
+                ("closest_hit", "point_pairs", "-", closest(t_pd))]
+    rows = []
+    for what, rays, tmax, launch in variants:
+        cnt.zero_()
+        torch.cuda.synchronize()
+        launch(cnt.data_ptr())
+        torch.cuda.synchronize()
+        row = {"what": what, "rays": rays, "tmax": tmax, "ms": []}
+        if what == "occluded":
+            row["occluded_fraction"] = round(int(cnt.item()) / n, 4)
+        for _ in range(3):
+            launch()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(args.reps):
+            launch()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        per = e0.elapsed_time(e1) / args.reps
+        row["reps"] = int(min(2000, max(args.reps, 50.0 / max(per, 1e-6))))
+        rows.append((row, launch))
+    for _ in range(args.windows):          # interleaved, as run_step
+        for row, launch in rows:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(row["reps"]):
+                launch()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            row["ms"].append(e0.elapsed_time(e1) / row["reps"])
+    res = {"step": step, "config": cname, "rays": n, "windows": args.windows, "results": []}
+    for row, _ in rows:
+        med = statistics.median(row["ms"])
+        r = {k: v for k, v in row.items() if k not in ("ms", "reps")}
+        r.update({"launches_per_window": row["reps"], "ms_median": round(med, 5),
+                  "ms_min": round(min(row["ms"]), 5), "ms_max": round(max(row["ms"]), 5),
+                  "ns_per_ray": round(med * 1e6 / n, 4)})
+        res["results"].append(r)
+    rend.close()
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", default=ALL_STEPS)
+    ap.add_argument("--steps", default="")
+    ap.add_argument("--occluded", action="store_true",
+                    help="the occlusion query against closest-hit (steps occluded_cN)")
     ap.add_argument("--rays", type=int, default=2_000_000)
     ap.add_argument("--reps", type=int, default=20, help="launches per timed window, at least")
     ap.add_argument("--windows", type=int, default=5)
@@ -162,10 +250,13 @@ def main():
     if args.reps < 20:
         ap.error("--reps must be at least 20")
     if args.step:
-        run_step(args.step, args)
+        if args.step.startswith("occluded_"):
+            run_occluded_step(args.step, args)
+        else:
+            run_step(args.step, args)
         return 0
     steps = []
-    for step in args.steps.split(","):
+    for step in (args.steps or (OCCLUDED_STEPS if args.occluded else ALL_STEPS)).split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--rays", str(args.rays),
                "--reps", str(args.reps), "--windows", str(args.windows)]
         try:
