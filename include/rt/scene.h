@@ -138,7 +138,9 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
 
 /* Options of the GPU frame operator (not in the reference): device, precision
  * (RT_PREC_*; default RT_PREC_MIXED whose output equals the fp64 path), recursion
- * depth (default 10) and flags (RT_FLAG_SUN).  `devices` with more than one entry renders
+ * depth (default 10) and flags (RT_FLAG_SUN; RT_FLAG_SHADOWS: hard shadows of the point
+ * light, a ray to LIGHT_POS at every hit — not with RT_PREC_F32 or RT_FLAG_SUN, see rt_capi.h;
+ * rt_scene and rt_radiance honour it, rt_closest_hits and rt_occluded ignore it).  `devices` with more than one entry renders
  * every frame row-tiled across those GPUs and gathers it into devices[0] (rt_multi_*,
  * BASELINE config 4; `transport` RT_TRANSPORT_RCCL, or RT_TRANSPORT_COPY, which also takes
  * one GPU listed several times); one entry with RT_TRANSPORT_RCCL_LOOPBACK goes through

@@ -125,8 +125,34 @@ enum rt_out_format {
 };
 
 enum rt_flags {
-    RT_FLAG_SUN = 1u << 0   /* build-defined sun term (SUN_COLOR/SUN_DIRECTION, main.cpp:18-19,
+    RT_FLAG_SUN = 1u << 0,  /* build-defined sun term (SUN_COLOR/SUN_DIRECTION, main.cpp:18-19,
                                defined but unused by the reference); off = reference parity */
+    RT_FLAG_SHADOWS = 1u << 1
+    /* Hard shadows (off by default; off = reference parity, nothing changes).  At EVERY
+     * accepted hit of recursive_ray_tracing — every level, the last included, for frames and
+     * for ray-batch radiance — a ray is traced to the point light LIGHT_POS (main.cpp:14, the
+     * origin):
+     *   origin     sp = pos + col.normal * .0001   (main.cpp:111's start point: pos as
+     *              main.cpp:99 forms it, the normal un-normalised)
+     *   direction  sd = LIGHT_POS - sp = (0,0,0) - sp,  limit T = 1
+     * The hit is SHADOWED iff that segment is occluded by rt_occluded's definition: some object
+     * has c.distance > 0 and its parameter (a wall's t, a sphere's `projection`) is <= 1,
+     * compared in fp64 on the exact values; the hit object itself takes part like any other.
+     * A shadowed hit has diffuse_intensity = specular_intensity = 0, so local_color =
+     * mat.color * mat.ambient.  Ray paths, the sky and the metallic lerp are untouched.
+     * Shadow rays are not counted: d_segments / rt_stats::segments equal the unshadowed
+     * frame's.  sp == 0 exactly is unspecified.
+     * The decision runs on the exact fp64 path in every supported precision: RT_PREC_F64 and
+     * RT_PREC_PATH64 decide with the same bits (PATH64 keeps its fp32 colour); RT_PREC_MIXED
+     * is served by the F64 shadow kernels (output == F64).
+     * RT_ERR_UNSUPPORTED, before any launch: RT_PREC_F32 with the flag; RT_FLAG_SUN |
+     * RT_FLAG_SHADOWS; rt_tile_row_costs with the flag.
+     * With the flag set RT_OPT_PIXEL_PAIRS is ignored, RT_OPT_FRAME_BATCH launches such
+     * frames one at a time, RT_OPT_ROW_FEEDBACK neither samples nor reorders them, and
+     * RT_OPT_SUPERSAMPLE works (every sample is shadowed, the resolve is unchanged).  Row
+     * bands, rt_render_device_interleaved and rt_multi_* work as without it (pixels are
+     * independent).  rt_trace_rays* with out == NULL, rt_occluded* and rt_frame_boxes ignore
+     * the flag.  Other flag bits stay ignored. */
 };
 
 typedef struct rt_stats {

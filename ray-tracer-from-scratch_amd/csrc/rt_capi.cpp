@@ -312,6 +312,20 @@ int check_render_args(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int
     return RT_OK;
 }
 
+/* RT_FLAG_SHADOWS (rt_capi.h): the shadow kernels exist for the fp64-path precisions without
+ * the sun term; checked before anything is launched. */
+int check_shadow_flags(int32_t precision, uint32_t flags) {
+    if (!(flags & RT_FLAG_SHADOWS)) return RT_OK;
+    if (precision == RT_PREC_F32 || (flags & RT_FLAG_SUN)) return RT_ERR_UNSUPPORTED;
+    return RT_OK;
+}
+
+/* The frame launch: the shadow kernels (rt_trace_shadow.hip) for a flagged frame. */
+int launch_frame(const rt::KParams& p, int32_t precision, void* stream, void* done_event = nullptr) {
+    if (p.flags & rt::FLAG_SHADOWS) return rt::launch_trace_shadow(p, precision, stream, done_event);
+    return rt::launch_trace(p, precision, stream, done_event);
+}
+
 /* rt_supersample_camera's arithmetic (rt_capi.h: the operation order is part of the ABI). */
 int supersample_camera(const rt_camera* cam, int32_t s, rt_camera* out) {
     if (!cam || !out || (s != 1 && s != 2 && s != 4 && s != 8)) return RT_ERR_INVALID_ARG;
@@ -724,7 +738,8 @@ rt::KParams make_params(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, i
     }
     p.out = d_out;
     p.segs = d_segs;
-    p.pairs = (ctx->pixel_pairs && !ss_log2) ? 1 : 0;  // (one sample per lane when resolving)
+    // (one sample per lane when resolving; no two-pixel shadow kernels)
+    p.pairs = (ctx->pixel_pairs && !ss_log2 && !(flags & RT_FLAG_SHADOWS)) ? 1 : 0;
     p.stats = ctx->d_stats;
     // eye tables (rt_device.h) for the linear-scan kernels: the same fp64 operations, in
     // the same order, as sphere_exact / wall_exact on a ray starting at cam->position
@@ -1491,7 +1506,8 @@ static int prepare_rows(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t
             p.row_perm_n = gy;
             std::memcpy(p.row_perm, ctx->row_perm.data(), gy * sizeof(int16_t));
         }
-    } else if (ctx->feedback > 0 && !p.ss_log2 && ctx->fb_band == band && !ctx->fb_perm.empty()) {
+    } else if (ctx->feedback > 0 && !p.ss_log2 && !(p.flags & rt::FLAG_SHADOWS) && ctx->fb_band == band &&
+               !ctx->fb_perm.empty()) {
         const int nu = gy << ctx->fb_units_log2;
         if ((int)ctx->fb_perm.size() == nu && nu <= rt::ROW_PERM_MAX) {
             p.row_units_log2 = ctx->fb_units_log2;
@@ -1503,7 +1519,8 @@ static int prepare_rows(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t
     p.tile_cost = nullptr;
     if (ctx->feedback <= 0 || !ctx->row_perm.empty() || gy > rt::ROW_PERM_MAX || ctx->cost_pending)
         return RT_OK;
-    if (p.ss_log2) return RT_OK;  // supersampled frames are never sampled (no stamped kernels)
+    // supersampled and shadowed frames are never sampled (no stamped kernels)
+    if (p.ss_log2 || (p.flags & rt::FLAG_SHADOWS)) return RT_OK;
     if (!(ctx->fb_band == band)) {
         ctx->warm_left = ctx->fb_warm;  // a new band or scene: the first snapshot, then the warm ones
     } else if (ctx->warm_left > 0) {
@@ -1685,7 +1702,7 @@ static int launch_prepared(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int3
     HP(2);
     // RT_DRY_LAUNCH (diagnostic builds, tools/multi_host_cost.py): every host step of the
     // frame but the kernel launch, to separate the host's own work from the runtime's
-    const int e = RT_DRY_LAUNCH ? (int)hipSuccess : rt::launch_trace(p, precision, hs, done);
+    const int e = RT_DRY_LAUNCH ? (int)hipSuccess : launch_frame(p, precision, hs, done);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_trace");
     if (RT_DRY_LAUNCH) return RT_OK;
     st = isolate_after(ctx, hs, sampled);
@@ -1707,6 +1724,7 @@ static int render_device_impl(rt_ctx* ctx, const rt_camera* cam, int32_t row0, i
     g_hn++;
 #endif
     int st = check_render_args(ctx, cam, row0, nrows, depth, precision, out_format);
+    if (st == RT_OK) st = check_shadow_flags(precision, flags);
     if (st != RT_OK) return st;
     if (!d_out && nrows > 0 && cam->width > 0) return RT_ERR_INVALID_ARG;
     if (ctx->ss_log2 && nparts > 1) return RT_ERR_UNSUPPORTED;  // contiguous bands only
@@ -1851,8 +1869,9 @@ static int launch_frame_groups(rt_ctx* ctx, const rt_camera* cams, int32_t ncams
             if (st != RT_OK) break;
             const bool other_grid = n > 0 && (p.W != grp[0].W || p.nrows != grp[0].nrows ||
                                               p.row_units_log2 != grp[0].row_units_log2);
-            // (no table kernels for the cull, pair and supersample paths: one launch each)
-            if (p.tile_cost || other_grid || p.wave_cull || p.pairs || p.ss_log2) {
+            // (no table kernels for the cull, pair, supersample and shadow paths: one launch each)
+            if (p.tile_cost || other_grid || p.wave_cull || p.pairs || p.ss_log2 ||
+                (p.flags & rt::FLAG_SHADOWS)) {
                 // this frame alone (after the frames grouped so far), through the per-frame path
                 const rt::KParams one = p;
                 st = launch_group(ctx, s, n, cam0, row0, nrows, precision, hs);
@@ -1940,6 +1959,7 @@ int rt_render_device_frames(rt_ctx* ctx, const rt_camera* cams, int32_t ncams, i
     if (!ctx || !cams || ncams <= 0 || !d_outs || nouts <= 0 || nframes < 0 ||
         (nstreams > 0 && !streams) || nstreams < 0)
         return RT_ERR_INVALID_ARG;
+    if (nframes > 0 && check_shadow_flags(precision, flags) != RT_OK) return RT_ERR_UNSUPPORTED;
     if (ctx->host_pipeline && nframes >= 2 && !RT_DRY_LAUNCH) {
         // every frame's arguments checked up front (the pipeline's helper computes them
         // unchecked); a batch with an invalid frame takes the sequential loop, which stops
@@ -1966,6 +1986,7 @@ int rt_render(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows, in
               int32_t precision, uint32_t flags, int32_t out_format, void* out,
               int32_t count_segments, rt_stats* stats) {
     int st = check_render_args(ctx, cam, row0, nrows, depth, precision, out_format);
+    if (st == RT_OK) st = check_shadow_flags(precision, flags);
     if (st != RT_OK) return st;
     const size_t bytes = (size_t)nrows * (size_t)cam->width * (size_t)bytes_per_pixel(out_format);
     if (!out && bytes > 0) return RT_ERR_INVALID_ARG;
@@ -1994,7 +2015,7 @@ int rt_render(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows, in
     st = prepare_rows(ctx, cam, row0, nrows, ctx->stream, p);
     if (st != RT_OK) return st;
     RT_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    const int e = rt::launch_trace(p, precision, ctx->stream);
+    const int e = launch_frame(p, precision, ctx->stream);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_trace");
     RT_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     st = snapshot_costs(ctx, cam, row0, nrows, ctx->stream, p);
@@ -2062,7 +2083,10 @@ int launch_ray_batch(rt_ctx* ctx, const double* d_origins, const double* d_direc
     ra.hits = reinterpret_cast<rt::DevHit*>(d_hits);
     ra.n = (int32_t)n;
     ra.shade = d_out ? 1 : 0;
-    const int e = rt::launch_rays(p, ra, prec, hs, done);
+    // RT_FLAG_SHADOWS: the shadow kernels (rt_rays_shadow.hip) shade; a hits-only call ignores it
+    if (d_out && (flags & RT_FLAG_SHADOWS) && (flags & RT_FLAG_SUN)) return RT_ERR_UNSUPPORTED;
+    const int e = (d_out && (flags & RT_FLAG_SHADOWS)) ? rt::launch_rays_shadow(p, ra, prec, hs, done)
+                                                       : rt::launch_rays(p, ra, prec, hs, done);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_rays");
     return RT_OK;
 }
@@ -2103,6 +2127,7 @@ int rt_trace_rays(rt_ctx* ctx, const double* origins, const double* directions, 
                   int32_t depth, int32_t precision, uint32_t flags, int32_t out_format, void* out,
                   rt_hit* hits, int32_t count_segments, rt_stats* stats) {
     int st = check_ray_args(ctx, origins, directions, n, depth, precision, out_format, out, hits);
+    if (st == RT_OK && out) st = check_shadow_flags(precision, flags);
     if (st != RT_OK) return st;
     if (n == 0) {
         if (stats) {
@@ -2251,6 +2276,7 @@ int rt_tile_row_costs(rt_ctx* ctx, const rt_camera* cam, int32_t depth, int32_t 
     const int32_t H = cam ? cam->height : 0;
     int st = check_render_args(ctx, cam, 0, H, depth, precision, RT_OUT_RGB_F32);
     if (st != RT_OK) return st;
+    if (flags & RT_FLAG_SHADOWS) return RT_ERR_UNSUPPORTED;  // no stamped shadow kernels
     const int gy = (H + rt::TILE_H - 1) / rt::TILE_H;
     if (!costs || n != gy) return RT_ERR_INVALID_ARG;
     if (gy == 0 || cam->width == 0) {

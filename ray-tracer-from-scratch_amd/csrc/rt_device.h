@@ -60,7 +60,7 @@ static_assert(sizeof(DevMat32) == 32, "material layout");
 
 enum { PREC_F64 = 0, PREC_F32 = 1, PREC_MIXED = 2, PREC_PATH64 = 3 };
 enum { OUT_RGB_F32 = 0, OUT_RGB_F64 = 1, OUT_RGBA8 = 2, OUT_RGBA8_WRAP = 3 };
-enum { FLAG_SUN = 1 };
+enum { FLAG_SUN = 1, FLAG_SHADOWS = 2 };
 
 // Pixel tile of one workgroup: RT_WAVES_PER_BLOCK waves (1, 2 or 4), each an 8x8 square.
 // One wave per workgroup measured fastest (tools/ab.py: c5 -15..21%, c3 -7..12%, c2 -2%
@@ -234,6 +234,10 @@ int launch_trace(const KParams& p, int prec, void* stream, void* done_event = nu
 int launch_trace_batch(const KParams* d_tab, const KParams& p0, int nframes, int prec, void* stream,
                        void* done_event);
 int max_depth();
+// A frame with FLAG_SHADOWS (rt_trace_shadow.hip): F64 (MIXED is served by it) and PATH64, one
+// pixel or one sample per lane, no sun, no frame table, no cost stamps; hipErrorInvalidValue
+// for anything else.
+int launch_trace_shadow(const KParams& p, int prec, void* stream, void* done_event);
 
 // Ray batches (rt_trace_rays*, rt_rays.hip): one lane per caller ray, ray blockIdx.x * BLOCK +
 // threadIdx.x.  The scene, depth, flags, output format and pointer, segment counter and cull
@@ -254,6 +258,8 @@ struct RayArgs {
 };
 // prec: PREC_F64 or PREC_PATH64 (anything else: hipErrorInvalidValue)
 int launch_rays(const KParams& p, const RayArgs& ra, int prec, void* stream, void* done_event);
+// The same with FLAG_SHADOWS (rt_rays_shadow.hip): radiance only (ra.shade), no sun.
+int launch_rays_shadow(const KParams& p, const RayArgs& ra, int prec, void* stream, void* done_event);
 
 // Occlusion queries (rt_occluded*, rt_rays.hip k_ray_occluded): is anything on the segment
 // o .. o + d * tmax of each caller ray?  Only the scene and cull fields of KParams are used.

@@ -129,7 +129,10 @@
 #ifndef RT_RAYS
 #define RT_RAYS 0   // 1 in rt_rays.hip: the device functions alone (namespace rt::kry), for the
 #endif              // ray-batch kernels; no frame kernel or launcher is compiled there
-#if RT_DIAG && (RT_STAMP || RT_RAYS)
+#ifndef RT_SHADOW
+#define RT_SHADOW 0 // 1 in rt_trace_shadow.hip (namespace rt::ksh) and rt_rays_shadow.hip (rt::krs):
+#endif              // RT_FLAG_SHADOWS' kernels, a ray to the light at every hit (light_blocked)
+#if RT_DIAG && (RT_STAMP || RT_RAYS || RT_SHADOW)
 #undef RT_DIAG
 #define RT_DIAG 0
 #endif
@@ -188,8 +191,12 @@ namespace rt {
 // s_memtime costs ~15% at c2 wherever it sits (tools/ab.py), so the plain kernels have none.
 #if RT_STAMP
 namespace kst {
+#elif RT_RAYS && RT_SHADOW
+namespace krs {
 #elif RT_RAYS
 namespace kry {
+#elif RT_SHADOW
+namespace ksh {
 #else
 namespace kno {
 #endif
@@ -1585,6 +1592,44 @@ __device__ __forceinline__ HitD scan_d(const KParams& p, const RayD& r, bool ali
     return h;
 }
 
+#if RT_SHADOW
+#include "rt_anyhit.h"
+
+/* RT_FLAG_SHADOWS: is the light hidden from the hit h of ray r?  The segment from
+ * sp = pos + col.normal * .0001 (main.cpp:111's start point: pos as main.cpp:99 forms it, a
+ * sphere's world distance used as t; the normal un-normalised) to LIGHT_POS = (0,0,0), i.e.
+ * direction LIGHT_POS - sp and limit T = 1, through the any-hit scan of the occlusion query —
+ * the linear scan, or the cull kernels' cone / cluster walk over the lanes that have a hit.
+ * Called converged (the cone's wave reductions need every lane present): lanes without a hit
+ * carry a harmless ray and take part only through todo == false.  Exact fp64 in every
+ * precision: pos and N are formed here again in fp64 whatever the caller shades in. */
+template <bool CULL>
+__device__ __forceinline__ bool light_blocked(const KParams& p, const RayD& r, const HitD& h,
+                                              bool alive) {
+    const bool open = alive && h.slot >= 0;
+    if (!__any(open)) return false;  // wave-uniform
+    d3 sp = D3(0.0, 0.0, 1.0);
+    if (open) {
+        const d3 pos = r.o + r.d * h.dist;
+        d3 N;
+        if (h.slot < p.nS) {
+            const double* S = p.s64[h.slot >> 2].v[h.slot & 3];
+            N = (r.o + r.d * h.pt) - D3(S[0], S[1], S[2]);
+        } else {
+            N = ld3(p.w64[h.slot - p.nS].n);
+        }
+        sp = pos + N * .0001;
+    }
+    const RayD sr = make_ray(sp, D3(0.0 - sp.x, 0.0 - sp.y, 0.0 - sp.z));
+    bool todo = open;
+    if (CULL)
+        occluded_cull(p, sr, todo, 1.0);
+    else
+        occluded_linear(p, sr, todo, 1.0);
+    return open && !todo;
+}
+#endif
+
 /* One pixel on the exact fp64 ray path.  COLOR64: colour arithmetic in fp64 too (F64 /
  * MIXED, the parity modes); otherwise in fp32 (PATH64). */
 template <bool MIXED, bool COLOR64, bool SUN, bool INT_EXP, bool CULL, int MAXD>
@@ -1701,6 +1746,11 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
             ray_terms(r);
             terms = true;
         }
+#if RT_SHADOW
+        // the light ray of every lane that hit, while the wave is still converged; not a
+        // counted segment.  A shadowed hit has diffuse = specular = 0: s = 0*kd + 0*ks + ka
+        const bool dark = light_blocked<CULL>(p, r, h, alive);
+#endif
         if (!alive) return;
         ++segs;
         if (!COLOR64 && RT_TERMINAL_F32 && (last || h.slot < 0)) {
@@ -1720,7 +1770,11 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
                 }
                 const DevMat32& m32 = p.mat32[h.slot];
                 const float2 sh = shade_f(m32, tof(pos), fnormalize(N32), nv32, sun);
+#if RT_SHADOW
+                c32 = local_color_f(m32, dark ? m32.ka : sh.x, sh.y, sun);
+#else
                 c32 = local_color_f(m32, sh.x, sh.y, sun);
+#endif
             }
             alive = false;
             return;
@@ -1764,6 +1818,9 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
             s = sh.x;
             ks = sh.y;
         }
+#if RT_SHADOW
+        if (dark) s = COLOR64 ? (CT)m.ka : (CT)p.mat32[h.slot].ka;
+#endif
         if (last) {
             if (COLOR64)
                 c64 = local_color_d(m, s, ks, sun);
@@ -2576,6 +2633,15 @@ constexpr int waves_per_eu() {
             (CULL ? RT_WPE_CULL64_BONUS : 0);
     return w < 2 ? 2 : w;
 }
+/* The shadow kernels (RT_SHADOW) keep the hit, the ray and the recursion state live across
+ * the light ray's scan: at their twins' targets the linear-scan kernels and the shallow PATH64
+ * cull kernels spilled 40-300 B per lane (`make asm`), so those run one wave per SIMD lower. */
+template <int PREC, bool CULL, int MAXD>
+constexpr int shadow_waves(int w) {
+    if (!RT_SHADOW) return w;
+    const int drop = !CULL ? 1 : ((PREC == PREC_PATH64 && MAXD < 10) ? 1 : 0);
+    return w - drop < 2 ? 2 : w - drop;
+}
 
 /* The store's pixel coordinates are formed again after the trace from the wave-uniform
  * tile (SGPRs) and the lane id read with v_mbcnt (not threadIdx.x, so the compiler cannot
@@ -2819,10 +2885,72 @@ __device__ __forceinline__ void trace_grid(const KParams& p) {
 #if !RT_RAYS  // the frame kernels and their launchers (not in rt_rays.hip)
 template <int PREC, bool SUN, bool INT_EXP, bool CULL, int MAXD, bool SS = false>
 __global__ void __launch_bounds__(BLOCK)
-__attribute__((amdgpu_waves_per_eu(waves_per_eu<PREC, SUN, INT_EXP, CULL, MAXD>(), 8)))
+__attribute__((amdgpu_waves_per_eu(
+    shadow_waves<PREC, CULL, MAXD>(waves_per_eu<PREC, SUN, INT_EXP, CULL, MAXD>()), 8)))
 k_trace(KParams p) {
     trace_grid<PREC, SUN, INT_EXP, CULL, MAXD, SS>(p);
 }
+
+#if RT_SHADOW
+/* The shadow unit's launchers: {F64, PATH64} x {linear, cull} x the four depth tiers, F64 with
+ * the general pow() at the deepest tier only (as the ray kernels, rays_depth), each plain and
+ * resolving (SS) — 36 kernels.  No sun, F32, pair, table or stamped variants. */
+template <int PREC, bool INT_EXP, bool CULL, int MAXD, bool SS>
+static void launch_one_sh(const KParams& p, dim3 grid, hipStream_t st, hipEvent_t done) {
+    if (done)
+        hipExtLaunchKernelGGL((k_trace<PREC, false, INT_EXP, CULL, MAXD, SS>), grid, dim3(BLOCK), 0, st,
+                              nullptr, done, 0, p);
+    else
+        hipLaunchKernelGGL((k_trace<PREC, false, INT_EXP, CULL, MAXD, SS>), grid, dim3(BLOCK), 0, st, p);
+}
+template <int PREC, bool INT_EXP, bool CULL, bool SS>
+static hipError_t launch_depth_sh(const KParams& p, dim3 grid, hipStream_t st, hipEvent_t done) {
+    if constexpr (!INT_EXP) {
+        launch_one_sh<PREC, false, CULL, MAXD_LARGE, SS>(p, grid, st, done);
+    } else {
+        if (p.depth <= MAXD_SMALL)
+            launch_one_sh<PREC, true, CULL, MAXD_SMALL, SS>(p, grid, st, done);
+        else if (p.depth <= MAXD_MID)
+            launch_one_sh<PREC, true, CULL, MAXD_MID, SS>(p, grid, st, done);
+        else if (p.depth <= MAXD_REF)
+            launch_one_sh<PREC, true, CULL, MAXD_REF, SS>(p, grid, st, done);
+        else
+            launch_one_sh<PREC, true, CULL, MAXD_LARGE, SS>(p, grid, st, done);
+    }
+    return hipGetLastError();
+}
+template <int PREC, bool SS>
+static hipError_t launch_prec_sh(const KParams& p, dim3 grid, hipStream_t st, hipEvent_t done) {
+    // (PATH64's fp32 colour takes the exponent through v_log / v_exp either way)
+    if (PREC == PREC_PATH64 || p.int_exp)
+        return p.wave_cull ? launch_depth_sh<PREC, true, true, SS>(p, grid, st, done)
+                           : launch_depth_sh<PREC, true, false, SS>(p, grid, st, done);
+    if constexpr (PREC == PREC_F64)
+        return p.wave_cull ? launch_depth_sh<PREC, false, true, SS>(p, grid, st, done)
+                           : launch_depth_sh<PREC, false, false, SS>(p, grid, st, done);
+    return hipErrorInvalidValue;
+}
+int launch_shadow_ns(const KParams& p, int prec, void* stream, void* done_event) {
+    if (p.W <= 0 || p.nrows <= 0) return (int)hipSuccess;
+    if (p.depth < 0 || p.depth > MAXD_LARGE || (p.flags & FLAG_SUN) || RT_TILE_PAIRS)
+        return (int)hipErrorInvalidValue;
+    const int ul = p.row_units_log2;
+    const int units = ((p.nrows + TILE_H - 1) / TILE_H) << ul;
+    const dim3 grid((((p.W + TILE_W - 1) / TILE_W) + (1 << ul) - 1) >> ul, units, 1);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipEvent_t done = static_cast<hipEvent_t>(done_event);
+    if (prec == PREC_MIXED) prec = PREC_F64;  // MIXED's contract is output == F64
+    if (prec != PREC_F64 && prec != PREC_PATH64) return (int)hipErrorInvalidValue;
+    if (p.ss_log2) {  // RT_OPT_SUPERSAMPLE: launch_trace_ns' conditions
+        if (p.ss_log2 < 0 || p.ss_log2 > 3 || p.tstride > 1 || ((p.W | p.nrows) & ((1 << p.ss_log2) - 1)))
+            return (int)hipErrorInvalidValue;
+        return (int)(prec == PREC_F64 ? launch_prec_sh<PREC_F64, true>(p, grid, st, done)
+                                      : launch_prec_sh<PREC_PATH64, true>(p, grid, st, done));
+    }
+    return (int)(prec == PREC_F64 ? launch_prec_sh<PREC_F64, false>(p, grid, st, done)
+                                  : launch_prec_sh<PREC_PATH64, false>(p, grid, st, done));
+}
+#else  // !RT_SHADOW
 
 #if !RT_STAMP
 /* A batch of frames of one band in ONE launch (rt_render_device_frames with
@@ -3125,12 +3253,17 @@ int launch_unit_max_ns(const uint16_t* cost, int gy, int gx, int ul, uint32_t* u
     return (int)hipGetLastError();
 }
 #endif  // !RT_STAMP
+#endif  // !RT_SHADOW
 #endif  // !RT_RAYS
 
-}  // namespace kno / kst / kry
+}  // namespace kno / kst / kry / ksh / krs
 
 #if RT_RAYS
 // rt_rays.hip defines its kernels and launch_rays behind this file
+#elif RT_SHADOW
+int launch_trace_shadow(const KParams& p, int prec, void* stream, void* done_event) {
+    return ksh::launch_shadow_ns(p, prec, stream, done_event);
+}
 #elif RT_STAMP
 int launch_trace_stamped(const KParams& p, int prec, void* stream, void* done_event) {
     return kst::launch_trace_ns(p, prec, stream, done_event);

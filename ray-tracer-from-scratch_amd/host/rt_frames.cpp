@@ -16,13 +16,15 @@
  *
  *   rt_frames [--frames N] [--keys wwaassdd] [--width W] [--depth D] [--precision f64|mixed|
  *             path64|f32] [--scene default|synthetic:S,W[,seed]] [--ppm file] [--gpu-surface]
- *             [--supersample 1|2|4|8]
+ *             [--supersample 1|2|4|8] [--shadows]
  *
  * --gpu-surface replaces rt_scene + the host packing loop by one rt_render with the
  * kernel's RT_OUT_RGBA8_WRAP epilogue: the same bytes main.cpp:345 produces, highlights
  * above 1.0 wrapping modulo 256 as the reference's x86-64 build does.
  * --supersample S traces S x S rays per pixel and stores their mean (RT_OPT_SUPERSAMPLE;
  * not in the reference: anti-aliased frames), on either path.
+ * --shadows sets RT_FLAG_SHADOWS (hard shadows of the point light; not in the reference), on
+ * either path; not with --precision f32.
  */
 #include <chrono>
 #include <cmath>
@@ -52,6 +54,7 @@ struct Args {
     std::string ppm;
     bool gpu_surface = false;
     int supersample = 1;
+    bool shadows = false;
 };
 
 int parse_precision(const std::string& s) {
@@ -82,6 +85,7 @@ Args parse(int argc, char** argv) {
         else if (o == "--scene") a.scene = val();
         else if (o == "--ppm") a.ppm = val();
         else if (o == "--gpu-surface") a.gpu_surface = true;
+        else if (o == "--shadows") a.shadows = true;
         else if (o == "--supersample") {
             a.supersample = std::atoi(val().c_str());
             if (a.supersample != 1 && a.supersample != 2 && a.supersample != 4 && a.supersample != 8) {
@@ -170,6 +174,7 @@ int main(int argc, char** argv) {
     opts.depth = a.depth;
     opts.precision = a.precision;
     opts.supersample = a.supersample;
+    if (a.shadows) opts.flags |= RT_FLAG_SHADOWS;
     rt_scene_set_options(opts);
 
     const int W = a.width, H = (int)cam.image_height;
@@ -214,7 +219,7 @@ int main(int argc, char** argv) {
             }
             c.width = W;
             c.height = H;
-            if (rt_render(ctx, &c, 0, H, a.depth, a.precision, 0, RT_OUT_RGBA8_WRAP, surface.data(), 0,
+            if (rt_render(ctx, &c, 0, H, a.depth, a.precision, opts.flags, RT_OUT_RGBA8_WRAP, surface.data(), 0,
                           nullptr) != RT_OK) {
                 std::fprintf(stderr, "rt_render failed: %s\n", rt_last_hip_error(ctx));
                 return 1;

@@ -54,6 +54,7 @@ RT_OUT_RGBA8 = 2
 RT_OUT_RGBA8_WRAP = 3
 
 RT_FLAG_SUN = 1
+RT_FLAG_SHADOWS = 2          # hard shadows: a ray to the light at every hit (F64, MIXED, PATH64)
 
 RT_OPT_WAVE_CULL_MIN_SPHERES = 1
 RT_OPT_STATS_DEVICE_PTR = 2
