@@ -207,8 +207,8 @@ enum rt_option {
                                          tile's cost; every N frames (and at once for a new
                                          band or scene) a snapshot is copied back behind the
                                          kernel, and later renders of the same band dispatch
-                                         tile rows heaviest-first by it (scheduling only);
-                                         0 = off.  Setting it (any value) drops the order
+                                         tile rows heaviest-first by it, or in
+                                         RT_OPT_ROW_MIX's order (scheduling only); 0 = off.  Setting it (any value) drops the order
                                          and any snapshot still in flight.  Output is
                                          identical. */
     RT_OPT_PIXEL_PAIRS = 9,           /* 1: RT_PREC_PATH64 renders without the wave cull
@@ -236,6 +236,23 @@ enum rt_option {
                                          overlapping frames; 0 (default) = it overlaps like
                                          any frame (measured: the lost overlap costs more
                                          than cleaner costs gain).  Output is identical. */
+    RT_OPT_ROW_MIX = 23,              /* How RT_OPT_ROW_FEEDBACK's measured order arranges
+                                         the dispatch units.  0 = strictly heaviest first
+                                         (by a unit's most expensive wave).  1 (default) =
+                                         for the frames of an rt_render_device_frames call
+                                         spread over two or more streams, the light units
+                                         (work, the sum of a unit's wave costs, not above
+                                         the mean) are merged between the heavy ones,
+                                         lightest first and in proportion to the work
+                                         dispatched, and the very lightest are held back
+                                         for the end: heavy (VALU-bound) and light
+                                         (issue-bound) waves share the SIMDs for the whole
+                                         frame, and the next frame in flight fills the
+                                         tail; frames rendered one at a time keep 0's order
+                                         (measured at c2: the mixed order alone on the GPU
+                                         is +15%, its tail exposed).  2 = the mixed order for
+                                         every frame (diagnostic).  rt_order_units gives
+                                         both orders on the host.  Output is identical. */
     RT_OPT_HOST_PIPELINE = 16,       /* 1 (default): rt_render_device_frames computes the
                                          next frames' kernel arguments (pixel boxes, mirror
                                          chains, eye tables) on a helper thread while the
@@ -665,6 +682,23 @@ int rt_band_rows(int32_t height, int32_t nranks, int32_t rank, int32_t* row0, in
  * (*nbox and *mir_depth are still set). */
 int rt_frame_boxes(const rt_prim* prims, int32_t n, const rt_camera* cam, int32_t row0,
                    int32_t nrows, int16_t* out, int32_t cap, int32_t* nbox, int32_t* mir_depth);
+
+/* Diagnostics, host only (no device): the dispatch order RT_OPT_ROW_FEEDBACK derives from a
+ * cost snapshot of n <= 2048 dispatch units (unit_max[u]: the unit's most expensive wave,
+ * clamped to 65535; unit_sum[u]: the sum of its waves' costs), by the function the frame
+ * loop uses.  mode 0 = heaviest first by unit_max, ties to the lower unit; mode 1 =
+ * RT_OPT_ROW_MIX's mixed order.  perm receives n unit indices.  RT_ERR_INVALID_ARG for
+ * n < 0, n > 2048, a null pointer or another mode. */
+int rt_order_units(const uint32_t* unit_max, const uint32_t* unit_sum, int32_t n, int32_t mode,
+                   int16_t* perm);
+
+/* Diagnostics: the row feedback's reduction kernel on caller-supplied wave costs (host
+ * array of gy rows of gx 16-bit costs): with 2^units_log2 dispatch units per row of
+ * U = ceil(gx / 2^units_log2) waves, unit_max and unit_sum (host, gy << units_log2 words
+ * each) receive every unit's maximum and sum.  Synchronous.  RT_ERR_INVALID_ARG for null
+ * pointers, gy or gx outside [1, 65535], units_log2 outside [0, 3]. */
+int rt_unit_costs(rt_ctx* ctx, const uint16_t* cost, int32_t gy, int32_t gx, int32_t units_log2,
+                  uint32_t* unit_max, uint32_t* unit_sum);
 
 /* Largest depth the kernels are compiled for (depth 0..rt_max_depth()). */
 int32_t rt_max_depth(void);

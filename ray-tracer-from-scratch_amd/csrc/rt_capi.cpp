@@ -17,6 +17,9 @@
 #ifndef RT_PIXEL_PAIRS_DEFAULT  // build-time default of RT_OPT_PIXEL_PAIRS (A/B builds)
 #define RT_PIXEL_PAIRS_DEFAULT 0
 #endif
+#ifndef RT_ROW_MIX_DEFAULT      // build-time default of RT_OPT_ROW_MIX (A/B builds)
+#define RT_ROW_MIX_DEFAULT 1
+#endif
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,9 +106,10 @@ struct rt_ctx {
     int ss_log2 = 0;               // RT_OPT_SUPERSAMPLE: S = 2^ss_log2 rays per pixel side
     uint16_t* d_cost = nullptr;    // device, d_cost_cap entries (one per wave)
     size_t d_cost_cap = 0;
-    uint32_t* d_umax = nullptr;    // device, per dispatch unit: its most expensive wave
+    uint32_t* d_umax = nullptr;    // device, per dispatch unit: its most expensive wave, then
+                                   // (behind the nu maxima) the sum of its waves: 2 nu words
     uint32_t* h_umax = nullptr;    // pinned host snapshot of d_umax
-    size_t umax_cap = 0;
+    size_t umax_cap = 0;           // in units (the buffers hold 2 words per unit)
     int cost_ul = 0;               // units per tile row (log2) of the pending snapshot
     hipEvent_t ev_cost = nullptr;  // snapshot landed
     bool cost_pending = false;
@@ -130,14 +134,29 @@ struct rt_ctx {
     };
     unsigned fb_epoch = 0;  // a snapshot still in flight from an older epoch is not used
     Band cost_band;                // band of the pending snapshot
-    Band fb_band;                  // band fb_perm was computed for
-    std::vector<int16_t> fb_perm;  // over dispatch units: 2^fb_units_log2 per tile row
+    Band fb_band;                  // band fb.perm was computed for
+    // order_units' results and working vectors (no allocation in steady state)
+    struct UnitOrder {
+        std::vector<int16_t> perm;  // heaviest first, over dispatch units: 2^fb_units_log2 per tile row
+        std::vector<int16_t> mix;   // RT_OPT_ROW_MIX: perm with the light units merged in (mix_units)
+        std::vector<float> acc;     // RT_OPT_ROW_FEEDBACK_EMA: per-unit smoothed maximum, for fb_band
+        std::vector<uint32_t> work; // per-unit sum of the waves' costs (smoothed alike)
+        std::vector<uint16_t> key;
+        std::vector<int16_t> tmp, heavy, light;
+    };
+    UnitOrder fb;
+    // RT_OPT_ROW_MIX: 0 = heaviest first; 1 (default) = the mixed order for the frames of an
+    // rt_render_device_frames call spread over several streams (frames_overlap), whose tail
+    // the next frame fills; 2 = the mixed order for every frame
+    int row_mix = RT_ROW_MIX_DEFAULT;
+    bool frames_overlap = false;   // inside rt_render_device_frames with >= 2 distinct streams
+    bool last_of_call = false;     // ... and this frame is the call's last: nothing is known to
+                                   // follow it, so its tail counts as exposed (heaviest first)
     int fb_units_log2 = 0;
     // RT_OPT_ROW_FEEDBACK_EMA: per-unit cost smoothed over the snapshots of one band
     // (acc = w*acc + (1-w)*new), so one noisy snapshot (tile costs measured while another
     // frame's waves shared the GPU) does not reorder the rows on its own; 0 = off
     int fb_ema = 0;                // w in percent
-    std::vector<float> fb_acc;     // per dispatch unit, for fb_band
 
     int since_snapshot = 0;
     // RT_OPT_ROW_FEEDBACK_WARM: after a new band or scene, this many further snapshots are
@@ -1393,6 +1412,10 @@ int rt_set_option(rt_ctx* ctx, int32_t option, int64_t value) {
             if (value != 0 && value != 1) return RT_ERR_INVALID_ARG;
             ctx->fb_isolate = value == 1;
             return RT_OK;
+        case RT_OPT_ROW_MIX:
+            if (value < 0 || value > 2) return RT_ERR_INVALID_ARG;
+            ctx->row_mix = (int)value;
+            return RT_OK;
         case RT_OPT_ROW_FEEDBACK_WARM:
             if (value < 0 || value > 1000) return RT_ERR_INVALID_ARG;
             ctx->fb_warm = (int)value;
@@ -1402,7 +1425,8 @@ int rt_set_option(rt_ctx* ctx, int32_t option, int64_t value) {
             ctx->feedback = (int)value;
             ctx->fb_epoch++;  // orders and snapshots taken so far belong to the old setting
             if (value == 0) {
-                ctx->fb_perm.clear();
+                ctx->fb.perm.clear();
+                ctx->fb.mix.clear();
                 ctx->fb_band = rt_ctx::Band{};
             }
             return RT_OK;
@@ -1452,34 +1476,139 @@ static int units_log2(int gy, int gx) {
     return 0;
 }
 
+#ifndef RT_ROW_MIX_TAIL_PERMILLE
+#define RT_ROW_MIX_TAIL_PERMILLE 20
+#endif
+/* RT_OPT_ROW_MIX: o.mix = o.perm (heaviest first) with the light units merged between the
+ * heavy ones, so that waves of both kinds share the SIMDs for the whole frame instead of a
+ * heavy phase (VALU-bound) followed by a light one (issue-bound, VALU half idle).
+ *  - heavy = a unit whose work (the sum of its waves' costs, o.work) is above the mean, plus
+ *    the first unit of o.perm whatever its work; the heavy units keep o.perm's order;
+ *  - the lightest units (from the end of o.perm: at least one, then while they total
+ *    <= RT_ROW_MIX_TAIL_PERMILLE / 1000 of the frame's work, about one fill of the chip at
+ *    c2) are held back for the end, so the frame drains on short waves;
+ *  - the other light units are drawn lightest first, each when the light work dispatched
+ *    has fallen behind the heavy work's share (cl / TL < ch / TH, in exact integers).
+ * No unit above the mean (all equal): o.mix = o.perm.  One pass, O(nu), no allocation once
+ * the vectors have their size.
+ * Measured alternatives at c2 PATH64, tile rows through rt_set_row_order, two frames in
+ * flight, us/frame (profiles/r07/probes/row_mix_probe.jsonl): heaviest first 27.07; this
+ * merge 25.37; the same with the light units drawn heaviest first 27.19; no held-back tail
+ * (light heaviest first) 30.47; a tail of 50/1000 25.44. */
+static void mix_units(rt_ctx::UnitOrder& o, int nu) {
+    const std::vector<int16_t>& s = o.perm;
+    std::vector<int16_t>& out = o.mix;
+    out.assign(s.begin(), s.end());
+    uint64_t total = 0;
+    for (int u = 0; u < nu; u++) total += o.work[u];
+    std::vector<int16_t>& hv = o.heavy;
+    std::vector<int16_t>& lt = o.light;
+    hv.clear();
+    lt.clear();
+    bool above = false;
+    for (int k = 0; k < nu; k++) {
+        const bool h = (uint64_t)o.work[s[k]] * (uint64_t)nu > total;
+        above |= h;
+        (h || k == 0 ? hv : lt).push_back(s[k]);
+    }
+    if (!above || lt.empty()) return;
+    // lt[m ..): the held-back tail
+    size_t m = lt.size() - 1;
+    uint64_t tail = o.work[lt[m]];
+    while (m > 0 && (tail + o.work[lt[m - 1]]) * 1000u <= total * (uint64_t)RT_ROW_MIX_TAIL_PERMILLE)
+        tail += o.work[lt[--m]];
+    uint64_t th = 0, tl = 0;
+    for (int16_t u : hv) th += o.work[u];
+    for (size_t j = 0; j < m; j++) tl += o.work[lt[j]];
+    typedef unsigned __int128 u128;
+    uint64_t ch = 0, cl = 0;
+    size_t i = 0, j = m, k = 0;  // the light units are drawn from lt[m - 1] down to lt[0]
+    while (i < hv.size() || j > 0) {
+        if (i < hv.size() && (j == 0 || (u128)cl * th >= (u128)ch * tl)) {
+            ch += o.work[hv[i]];
+            out[k++] = hv[i++];
+        } else {
+            cl += o.work[lt[--j]];
+            out[k++] = lt[j];
+        }
+    }
+    for (size_t t = m; t < lt.size(); t++) out[k++] = lt[t];
+}
+
 /* Dispatch units ordered by their most expensive wave (heaviest first; ties keep the lower
- * unit), from the per-unit maxima of a cost snapshot (k_unit_max).  Host work is O(nu):
+ * unit), from the per-unit maxima of a cost snapshot (k_unit_max_sum); the units' sums are
+ * their work for the mixed order (mix_units).  Host work is O(nu):
  * the keys are 16-bit (wave costs saturate at 65535), sorted by a stable two-pass radix
  * sort — the comparison sort it replaces took ~100 us on the thread that enqueues frames,
  * long enough to starve the GPU once per snapshot. */
-static void order_units(const uint32_t* umax, int nu, std::vector<int16_t>& perm,
-                        std::vector<float>& acc, bool acc_valid, int ema) {
+static void order_units(const uint32_t* umax, const uint32_t* usum, int nu, rt_ctx::UnitOrder& o,
+                        bool acc_valid, int ema) {
     // smoothed over the band's snapshots (RT_OPT_ROW_FEEDBACK_EMA), else this snapshot's
     const float w = ema / 100.0f;
-    const bool smooth = acc_valid && (int)acc.size() == nu && ema > 0;
-    if (!smooth) acc.assign(nu, 0.0f);
-    std::vector<uint16_t> key(nu);
+    const bool smooth = acc_valid && (int)o.acc.size() == nu && (int)o.work.size() == nu && ema > 0;
+    if (!smooth) {
+        o.acc.assign(nu, 0.0f);
+        o.work.assign(nu, 0u);
+    }
+    o.key.resize(nu);
     for (int u = 0; u < nu; u++) {
         const float m = (float)std::min<uint32_t>(umax[u], 65535u);
-        const float a = smooth ? w * acc[u] + (1.0f - w) * m : m;
-        acc[u] = a;
-        key[u] = (uint16_t)(65535u - (uint32_t)std::min(a + 0.5f, 65535.0f));  // descending
+        const float a = smooth ? w * o.acc[u] + (1.0f - w) * m : m;
+        o.acc[u] = a;
+        o.key[u] = (uint16_t)(65535u - (uint32_t)std::min(a + 0.5f, 65535.0f));  // descending
+        o.work[u] = smooth ? (uint32_t)(w * (float)o.work[u] + (1.0f - w) * (float)usum[u] + 0.5f) : usum[u];
     }
-    std::vector<int16_t> tmp(nu);
+    std::vector<int16_t>& perm = o.perm;
+    std::vector<int16_t>& tmp = o.tmp;
+    tmp.resize(nu);
     perm.resize(nu);
     for (int u = 0; u < nu; u++) perm[u] = (int16_t)u;
     for (int sh = 0; sh < 16; sh += 8) {
         unsigned cnt[257] = {0};
-        for (int k = 0; k < nu; k++) cnt[((key[perm[k]] >> sh) & 255) + 1]++;
+        for (int k = 0; k < nu; k++) cnt[((o.key[perm[k]] >> sh) & 255) + 1]++;
         for (int b = 0; b < 256; b++) cnt[b + 1] += cnt[b];
-        for (int k = 0; k < nu; k++) tmp[cnt[(key[perm[k]] >> sh) & 255]++] = perm[k];
+        for (int k = 0; k < nu; k++) tmp[cnt[(o.key[perm[k]] >> sh) & 255]++] = perm[k];
         perm.swap(tmp);
     }
+    mix_units(o, nu);
+}
+
+/* Host-only diagnostic: the dispatch order order_units gives for these per-unit maxima and
+ * sums (mode 0: heaviest first, 1: the mixed order). */
+int rt_order_units(const uint32_t* unit_max, const uint32_t* unit_sum, int32_t n, int32_t mode,
+                   int16_t* perm) {
+    if (n < 0 || n > rt::ROW_PERM_MAX || !unit_max || !unit_sum || !perm || (mode != 0 && mode != 1))
+        return RT_ERR_INVALID_ARG;
+    rt_ctx::UnitOrder o;
+    order_units(unit_max, unit_sum, n, o, false, 0);
+    const std::vector<int16_t>& r = mode == 1 ? o.mix : o.perm;
+    std::copy(r.begin(), r.end(), perm);
+    return RT_OK;
+}
+
+/* Diagnostic: k_unit_max_sum on the caller's wave costs (buffers of its own, synchronous). */
+int rt_unit_costs(rt_ctx* ctx, const uint16_t* cost, int32_t gy, int32_t gx, int32_t units_log2,
+                  uint32_t* unit_max, uint32_t* unit_sum) {
+    if (!ctx || !cost || !unit_max || !unit_sum || gy < 1 || gy > 65535 || gx < 1 || gx > 65535 ||
+        units_log2 < 0 || units_log2 > 3)
+        return RT_ERR_INVALID_ARG;
+    DeviceGuard dg(ctx->device);
+    RT_HIP(ctx, dg.err);
+    const size_t nc = (size_t)gy * gx, nu = (size_t)gy << units_log2;
+    uint16_t* d_cost = nullptr;
+    uint32_t* d_stat = nullptr;
+    hipError_t e = hipMalloc(&d_cost, nc * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc(&d_stat, 2 * nu * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cost, cost, nc * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = (hipError_t)rt::launch_unit_max_sum(d_cost, gy, gx, units_log2, d_stat, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(unit_max, d_stat, nu * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(unit_sum, d_stat + nu, nu * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (d_cost) (void)hipFree(d_cost);
+    if (d_stat) (void)hipFree(d_stat);
+    RT_HIP(ctx, e);
+    RT_HIP(ctx, es);
+    return RT_OK;
 }
 
 /* Before a launch: the row order (explicit, else the feedback's for this band) and the
@@ -1497,7 +1626,8 @@ static int prepare_rows(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t
         const int ul = ctx->cost_ul;
         const bool same = ctx->fb_band == b && ctx->fb_units_log2 == ul;  // keep smoothing
         ctx->fb_units_log2 = ul;
-        order_units(ctx->h_umax, bgy << ul, ctx->fb_perm, ctx->fb_acc, same, ctx->fb_ema);
+        const int bnu = bgy << ul;
+        order_units(ctx->h_umax, ctx->h_umax + bnu, bnu, ctx->fb, same, ctx->fb_ema);
         ctx->fb_band = b;
     }
     p.row_units_log2 = 0;
@@ -1507,12 +1637,14 @@ static int prepare_rows(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t
             std::memcpy(p.row_perm, ctx->row_perm.data(), gy * sizeof(int16_t));
         }
     } else if (ctx->feedback > 0 && !p.ss_log2 && !(p.flags & rt::FLAG_SHADOWS) && ctx->fb_band == band &&
-               !ctx->fb_perm.empty()) {
+               !ctx->fb.perm.empty()) {
         const int nu = gy << ctx->fb_units_log2;
-        if ((int)ctx->fb_perm.size() == nu && nu <= rt::ROW_PERM_MAX) {
+        const bool mix = ctx->row_mix == 2 || (ctx->row_mix == 1 && ctx->frames_overlap && !ctx->last_of_call);
+        const std::vector<int16_t>& perm = mix && ctx->fb.mix.size() == ctx->fb.perm.size() ? ctx->fb.mix : ctx->fb.perm;
+        if ((int)perm.size() == nu && nu <= rt::ROW_PERM_MAX) {
             p.row_units_log2 = ctx->fb_units_log2;
             p.row_perm_n = nu;
-            std::memcpy(p.row_perm, ctx->fb_perm.data(), nu * sizeof(int16_t));
+            std::memcpy(p.row_perm, perm.data(), nu * sizeof(int16_t));
         }
     }
     // sample this frame's costs when a snapshot is due (snapshot_costs copies them)
@@ -1547,8 +1679,8 @@ static int prepare_rows(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t
         ctx->d_cost_cap = 0;
         ctx->umax_cap = 0;
         RT_HIP(ctx, hipMalloc(&ctx->d_cost, cap * sizeof(uint16_t)));
-        RT_HIP(ctx, hipMalloc(&ctx->d_umax, ucap * sizeof(uint32_t)));
-        RT_HIP(ctx, hipHostMalloc(&ctx->h_umax, ucap * sizeof(uint32_t), hipHostMallocDefault));
+        RT_HIP(ctx, hipMalloc(&ctx->d_umax, 2 * ucap * sizeof(uint32_t)));
+        RT_HIP(ctx, hipHostMalloc(&ctx->h_umax, 2 * ucap * sizeof(uint32_t), hipHostMallocDefault));
         ctx->d_cost_cap = cap;
         ctx->umax_cap = ucap;
     }
@@ -1565,10 +1697,10 @@ static int snapshot_costs(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32
     const int gy = (nrows + rt::TILE_H - 1) / rt::TILE_H;
     const int gx = ((cam->width + rt::TILE_W - 1) / rt::TILE_W) * (rt::BLOCK / 64);
     const int ul = units_log2(gy, gx);
-    // per-unit maxima on the device, then nu words back (not every wave's cost)
-    const int e = rt::launch_unit_max(ctx->d_cost, gy, gx, ul, ctx->d_umax, st);
-    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_unit_max");
-    RT_HIP(ctx, hipMemcpyAsync(ctx->h_umax, ctx->d_umax, ((size_t)gy << ul) * sizeof(uint32_t),
+    // per-unit maxima and sums on the device, then 2 nu words back (not every wave's cost)
+    const int e = rt::launch_unit_max_sum(ctx->d_cost, gy, gx, ul, ctx->d_umax, st);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_unit_max_sum");
+    RT_HIP(ctx, hipMemcpyAsync(ctx->h_umax, ctx->d_umax, 2 * ((size_t)gy << ul) * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipEventRecord(ctx->ev_cost, st));
     ctx->cost_pending = true;
@@ -1865,6 +1997,7 @@ static int launch_frame_groups(rt_ctx* ctx, const rt_camera* cams, int32_t ncams
             st = virt_frame(ctx, &cams[f % ncams], row0, nrows, vf);
             if (st != RT_OK) break;
             const rt_camera* cam = vf.cam;
+            ctx->last_of_call = f + 1 == nframes;
             st = prepare_rows(ctx, cam, vf.row0, vf.nrows, hs, p);
             if (st != RT_OK) break;
             const bool other_grid = n > 0 && (p.W != grp[0].W || p.nrows != grp[0].nrows ||
@@ -1939,6 +2072,7 @@ static int render_frames_pipelined(rt_ctx* ctx, const rt_camera* cams, int32_t n
         for (int32_t f = 0; f < nframes; f++) {
             while (q.produced.load(std::memory_order_acquire) <= f) std::this_thread::yield();
             void* stf = nstreams > 0 ? streams[f % nstreams] : nullptr;
+            ctx->last_of_call = f + 1 == nframes;
             st = render_device_impl(ctx, &cams[f % ncams], row0, nrows, 0, 0, 0, depth, precision, flags,
                                     out_format, d_outs[f % nouts], nullptr, stf,
                                     &q.slot[f % rt_ctx::Prep::RING]);
@@ -1960,6 +2094,13 @@ int rt_render_device_frames(rt_ctx* ctx, const rt_camera* cams, int32_t ncams, i
         (nstreams > 0 && !streams) || nstreams < 0)
         return RT_ERR_INVALID_ARG;
     if (nframes > 0 && check_shadow_flags(precision, flags) != RT_OK) return RT_ERR_UNSUPPORTED;
+    // RT_OPT_ROW_MIX 1: consecutive frames on different streams overlap on the GPU
+    struct Overlap {
+        bool &f, &l;
+        ~Overlap() { f = l = false; }
+    } overlap{ctx->frames_overlap, ctx->last_of_call};
+    for (int32_t k = 1; k < nstreams && k < nframes; k++)
+        if (streams[k] != streams[0]) ctx->frames_overlap = true;
     if (ctx->host_pipeline && nframes >= 2 && !RT_DRY_LAUNCH) {
         // every frame's arguments checked up front (the pipeline's helper computes them
         // unchecked); a batch with an invalid frame takes the sequential loop, which stops
@@ -1975,6 +2116,7 @@ int rt_render_device_frames(rt_ctx* ctx, const rt_camera* cams, int32_t ncams, i
     }
     for (int32_t f = 0; f < nframes; f++) {
         void* st = nstreams > 0 ? streams[f % nstreams] : nullptr;
+        ctx->last_of_call = f + 1 == nframes;
         const int e = rt_render_device(ctx, &cams[f % ncams], row0, nrows, depth, precision,
                                        flags, out_format, d_outs[f % nouts], nullptr, st);
         if (e != RT_OK) return e;

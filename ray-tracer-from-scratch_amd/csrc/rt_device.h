@@ -279,9 +279,10 @@ int launch_occluded(const KParams& p, const OccArgs& oa, void* stream, void* don
 // pow: > 128 ulp) to *d_bad.
 int launch_selftest(int which, uint64_t n, uint64_t seed, unsigned long long* d_bad,
                     void* stream);
-// Row feedback: umax[(r << ul) + q] = the largest of cost[r * gx + q * U ..] over dispatch
-// unit q of row r (U = ceil(gx / 2^ul)), for gy rows of gx wave costs.
-int launch_unit_max(const uint16_t* cost, int gy, int gx, int ul, uint32_t* umax, void* stream);
+// Row feedback: with nu = gy << ul dispatch units, ustat[(r << ul) + q] = the largest and
+// ustat[nu + (r << ul) + q] = the sum of cost[r * gx + q * U ..] over dispatch unit q of row r
+// (U = ceil(gx / 2^ul)), for gy rows of gx wave costs.
+int launch_unit_max_sum(const uint16_t* cost, int gy, int gx, int ul, uint32_t* ustat, void* stream);
 
 }  // namespace rt
 

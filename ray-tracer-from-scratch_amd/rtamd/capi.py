@@ -78,6 +78,8 @@ RT_OPT_FRAME_BATCH = 21
 RT_OPT_SUPERSAMPLE = 22      # S in {1, 2, 4, 8}: S x S rays per pixel, mean stored (changes output)
 RT_OPT_ROW_FEEDBACK_EMA = 14
 RT_OPT_ROW_FEEDBACK_ISOLATE = 15
+RT_OPT_ROW_MIX = 23          # 0 heaviest first, 1 mixed for frames in flight on streams, 2 mixed always
+ROW_PERM_MAX = 2048          # dispatch units of a row order (rt_set_row_order, rt_order_units)
 
 
 class rt_material(C.Structure):
@@ -208,6 +210,11 @@ SIGNATURES = [
     ("rt_tile_row_costs", C.c_int,
      [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float),
       C.c_int32]),
+    ("rt_order_units", C.c_int,
+     [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.POINTER(C.c_int16)]),
+    ("rt_unit_costs", C.c_int,
+     [C.c_void_p, C.POINTER(C.c_uint16), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32),
+      C.POINTER(C.c_uint32)]),
 ]
 
 _lib = None
@@ -293,6 +300,23 @@ def frame_boxes(prims, cam: rt_camera, row0: int = 0, nrows: int | None = None):
                              C.byref(md)))
     n = nb.value
     return out[:n], out[n:], md.value
+
+
+def order_units(unit_max, unit_sum, mode: int = 0):
+    """rt_order_units (host only): the dispatch order the row feedback derives from per-unit
+    maxima and sums (mode 0 heaviest first, 1 RT_OPT_ROW_MIX's mixed order) -> int16 array."""
+    import numpy as np
+    lib = load()
+    mx = np.ascontiguousarray(unit_max, np.uint32)
+    sm = np.ascontiguousarray(unit_sum, np.uint32)
+    if mx.shape != sm.shape or mx.ndim != 1:
+        raise ValueError("unit_max and unit_sum differ in shape")
+    n = len(mx)
+    perm = np.zeros(max(1, n), np.int16)
+    check(lib.rt_order_units(mx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                             sm.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(mode),
+                             perm.ctypes.data_as(C.POINTER(C.c_int16))))
+    return perm[:n]
 
 
 def band_rows(height: int, nranks: int, rank: int) -> tuple[int, int]:
@@ -428,6 +452,18 @@ class Renderer:
         check(self.lib.rt_tile_row_costs(self.ctx, C.byref(cam), depth, precision, flags,
                                          out.ctypes.data_as(C.POINTER(C.c_float)), n), self.ctx)
         return out[:n]
+
+    def unit_costs(self, cost, units_log2: int):
+        """rt_unit_costs: the row feedback's reduction kernel on a [gy, gx] uint16 array of
+        wave costs -> (unit_max, unit_sum), uint32 arrays of gy << units_log2 units."""
+        c = np.ascontiguousarray(cost, np.uint16)
+        gy, gx = c.shape
+        nu = gy << units_log2
+        mx, sm = np.zeros(nu, np.uint32), np.zeros(nu, np.uint32)
+        check(self.lib.rt_unit_costs(self.ctx, c.ctypes.data_as(C.POINTER(C.c_uint16)), gy, gx,
+                                     units_log2, mx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                     sm.ctypes.data_as(C.POINTER(C.c_uint32))), self.ctx)
+        return mx, sm
 
     def render_device_interleaved(self, cam: rt_camera, depth: int, nparts: int, part: int,
                                   d_out: int, precision: int = RT_PREC_F64, flags: int = 0,
