@@ -1,7 +1,7 @@
 /* rt_anyhit.h — any-hit scans on the segment o .. o + d * T, for the occlusion query
- * (rt_rays.hip k_ray_occluded) and the light ray of RT_FLAG_SHADOWS (rt_trace.hip
+ * (rt_rays.hip k_ray_occluded) and the light ray of RT_FLAG_SHADOWS (rt_scan_dev.h
  * light_blocked).  Not a header of its own: it is included inside the namespace of a unit
- * that has rt_trace.hip's device functions in front of it (RayD, div_r, wave_cone,
+ * that has rt_scan_dev.h's device functions in front of it (RayD, div_r, wave_cone,
  * cull_chunk, clusters_mask, ...), once per unit.
  *
  * A lane is blocked as soon as one primitive j has a Collision c = scene[j]->intersect(ray)

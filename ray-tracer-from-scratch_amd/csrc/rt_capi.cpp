@@ -610,7 +610,7 @@ void frame_boxes(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t 
     }
     boxes_for(ctx, P, dmax, cam->width, row0, nrows, p.box);
     p.nbox = np;
-    // dispatch order (rt_trace.hip tile_row): centre-out from the weighted median tile row
+    // dispatch order (rt_frame_dev.h tile_row): centre-out from the weighted median tile row
     // of the boxes' coverage, reflective primitives weighted up (their tiles bounce)
     if (ctx->row_order) {
         const int nty = (nrows + 7) / 8;
@@ -780,7 +780,7 @@ rt::KParams make_params(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, i
     }
     // primary scan's wall order: nearest rectangle to the camera first, so the wall t-skip
     // (t > best) drops the bounds test of the walls it occludes.  Any order gives the
-    // reference's winner (wall ties compare scene indices, rt_trace.hip wall_exact).
+    // reference's winner (wall ties compare scene indices, rt_scan_dev.h wall_exact).
     p.wall_order_n = 0;
     p.wall_order = 0;
     if (ctx->wall_order && ctx->sc.nW > 1 && ctx->sc.nW <= 16) {

@@ -113,7 +113,7 @@ struct PrimBox {
     int16_t x0, x1, i0, i1;  // inclusive pixel box (frame rows); x0 > x1 = never hit
 };
 
-// Sphere clusters for the cull kernels' wide-cone waves (rt_trace.hip clusters_scan).  The
+// Sphere clusters for the cull kernels' wide-cone waves (rt_scan_dev.h clusters_scan).  The
 // host splits the spheres at the median of the centres' widest axis until each leaf holds
 // <= CLU_SIZE of them (rt_capi.cpp build_clusters); each leaf gets an fp32 box around its
 // balls widened by a margin far above fp32 rounding, and a copy of its spheres' exact fp64
@@ -169,7 +169,7 @@ struct KParams {
                              // every reflection / shading step normalises again
     int32_t nS, nW;
     int32_t int_exp;       // every specular exponent is an integer in [0, 1024]
-    int32_t wave_cull;     // cull spheres per wave (rt_trace.hip) before the per-lane tests
+    int32_t wave_cull;     // cull spheres per wave (rt_scan_dev.h) before the per-lane tests
     int32_t W, row0, nrows, depth;
     uint32_t flags;
     int32_t outf;
@@ -178,14 +178,14 @@ struct KParams {
     unsigned long long* segs;   // may be null
     unsigned long long* stats;  // diagnostic counters, may be null (rt_set_option)
     int32_t nbox;               // primitives with a PrimBox (nS + nW), 0 = tile bins off
-    int32_t row_center;         // tile row dispatched first (rt_trace.hip tile_row), -1 = off
+    int32_t row_center;         // tile row dispatched first (rt_frame_dev.h tile_row), -1 = off
     uint16_t* tile_cost;        // per wave (workgroup row-major over the frame's tiles, then
                                 // wave): shader cycles / 32, saturated; null = not recorded
     int32_t row_units_log2;     // each tile row split into 2^k dispatch units (k > 0 only
                                 // with a row_perm over units: unit u = row (u >> k), part
                                 // (u & (2^k - 1)) of ceil(tiles / 2^k) tiles)
     int32_t row_perm_n;         // dispatch units in row_perm (== the grid's rows), 0 = unused
-    int16_t row_perm[ROW_PERM_MAX];  // dispatch order of tile rows (rt_trace.hip tile_row)
+    int16_t row_perm[ROW_PERM_MAX];  // dispatch order of tile rows (rt_frame_dev.h tile_row)
     PrimBox box[BIN_MAX_PRIMS]; // material-slot order: spheres, then walls (scenes with the
                                 // wave cull: the walls' boxes only, box[w] = wall w)
     int32_t nwbox;              // wave-cull scenes: walls with a PrimBox in box[] (0 = off)
@@ -216,7 +216,7 @@ struct KParams {
     // RT_OPT_SUPERSAMPLE: S = 2^ss_log2 (0 = off).  W, row0, nrows and the camera are the
     // S-times larger frame's; the kernel stores the mean of each S x S square of its pixels
     // at row (band row >> ss_log2), column (x >> ss_log2) of an output W >> ss_log2 wide
-    // (rt_trace.hip ss_resolve).  Contiguous bands only.
+    // (rt_frame_dev.h ss_resolve).  Contiguous bands only.
     int32_t ss_log2;
 };
 // by-value kernel arguments of up to 16 KB arrive intact (tools/ubench/kernarg_size.hip,

@@ -372,7 +372,7 @@ def test_full_size_c5_properties(rend):
 
 # ---------------------------------------------------------------- exact helpers
 def test_selftest_shared_reciprocal_division_is_ieee(rend):
-    """rt_trace.hip shares one refined reciprocal across the numerators of a
+    """rt_scan_dev.h shares one refined reciprocal across the numerators of a
     normalisation; it must give IEEE `/`'s bits (division over 2^-40..2^40, both signs,
     and the component/|v| pattern)."""
     assert rend.selftest(0, 1 << 24, seed=12345) == 0

@@ -70,7 +70,7 @@ def tree_mean(frame, s):
 
 
 def q8(v):
-    """RT_OUT_RGBA8's conversion (rt_trace.hip q8): clamp to [0, 1], NaN -> 0, truncate v*255."""
+    """RT_OUT_RGBA8's conversion (rt_scan_dev.h q8): clamp to [0, 1], NaN -> 0, truncate v*255."""
     v = np.where(v > 0.0, v, 0.0)
     v = np.where(v < 1.0, v, 1.0)
     return (v * 255.0).astype(np.uint32)
