@@ -1,4 +1,4 @@
-"""The property the tile bins' host half must have (rt_frame_boxes, rt_capi.cpp frame_boxes),
+"""The property the tile bins' host half must have (rt_frame_boxes, rt_frame_args.cpp frame_boxes),
 checked against the oracle: every pixel whose path hits primitive j on its primary segment
 lies inside j's primary pixel box; every pixel whose primary ray hit wall w (and whose first
 bounce off it hit j) lies inside j's box for the camera mirrored in w; likewise for two-wall

@@ -1,4 +1,4 @@
-"""CPU check of the tile bins' host half (rt_frame_boxes, rt_capi.cpp frame_boxes): every
+"""CPU check of the tile bins' host half (rt_frame_boxes, rt_frame_args.cpp frame_boxes): every
 pixel whose path, in the oracle's fp64 restatement of the reference, hits primitive j on
 its primary segment lies inside j's primary pixel box; every pixel whose primary ray hit
 wall w (and whose first bounce off it hit j) lies inside j's box for the camera mirrored
@@ -63,10 +63,10 @@ def test_frame_boxes_errors():
 
 
 def test_frame_boxes_fuzz_bounds_and_capacity():
-    """Host-code fuzz of the per-frame box assembly (rt_capi.cpp pack_scene, frame_boxes,
-    boxes_for, the mirror-chain levels) — the hand-indexed host code `tools/asan_check.sh`
-    runs under AddressSanitizer/UBSan: random scene sizes up to past the 64-primitive bin
-    limit and 20 walls (mirror levels shrink with nW), degenerate primitives (zero and
+    """Host-code fuzz of the per-frame box assembly (rt_scene_pack.cpp pack_scene,
+    rt_frame_args.cpp frame_boxes, boxes_for, the mirror-chain levels) — the hand-indexed
+    host code `tools/asan_check.sh` runs under AddressSanitizer/UBSan: random scene sizes
+    up to past the 64-primitive bin limit and 20 walls (mirror levels shrink with nW), degenerate primitives (zero and
     negative radii, z-normal and NaN-normal walls, far coordinates), cameras inside
     primitives and with extreme fields of view, random row bands, and capacities exactly
     at and one below the box count.  Every returned box lies in the frame/band widened by

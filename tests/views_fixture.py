@@ -79,7 +79,7 @@ class Views:
 
 
 def int_exp(prims):
-    """rt_capi.cpp pack_scene: every specular exponent an integer in [0, 1024] selects the
+    """rt_scene_pack.cpp pack_scene: every specular exponent an integer in [0, 1024] selects the
     integer-pow kernels, anything else the general-pow ones."""
     return all(0.0 <= p.mat.specular_exponent <= 1024.0 and
                p.mat.specular_exponent == np.floor(p.mat.specular_exponent) for p in prims)

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # Host UBSan on the GPU paths (run on the GPU box through gpurun): the GPU test files against
 # lib/ubsan/librt_amd.so (`make ubsan`: UndefinedBehaviorSanitizer on the C-ABI's host code,
-# rt_capi.cpp and rt_multi.cpp — the multi-GPU exchange, the host pipeline — with the device
+# every csrc/*.cpp unit — the multi-GPU exchange, the host pipeline among them — with the device
 # code unchanged; the UBSan runtime is a dependency of the library, nothing is preloaded).
 # Any report aborts the test process (-fno-sanitize-recover).  Build it beforehand, here, and
 # take its line out of .gpurunignore for the run (it is listed there to keep pushes small).
