@@ -148,7 +148,16 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
  * `supersample` S in {1, 2, 4, 8} (default 1) makes rt_scene trace S x S rays per pixel and
  * store their mean (RT_OPT_SUPERSAMPLE, rt_capi.h; the ray queries below ignore it); it is
  * the one-GPU renderer's: with `devices` selecting the row-tiled operator, or any other
- * value, rt_scene throws std::invalid_argument before any device work. */
+ * value, rt_scene throws std::invalid_argument before any device work.
+ * `lights`: the scene's point lights (rt_set_lights, rt_capi.h "Lights": up to RT_MAX_LIGHTS,
+ * each a position and a colour factor; not with RT_PREC_F32 or RT_FLAG_SUN).  Empty (the
+ * default) means the reference's light, LIGHT_POS = (0,0,0), white.  rt_scene — the row-tiled
+ * `devices` path included — and rt_radiance honour them; rt_closest_hits and rt_occluded
+ * ignore them. */
+struct RtLight {
+    point3 position;
+    RGB color;
+};
 struct RtSceneOptions {
     int device = 0;
     int precision = RT_PREC_MIXED;
@@ -157,6 +166,7 @@ struct RtSceneOptions {
     std::vector<int> devices;
     int transport = RT_TRANSPORT_RCCL;
     int supersample = 1;
+    std::vector<RtLight> lights;
 };
 void rt_scene_set_options(const RtSceneOptions& opts);
 RtSceneOptions rt_scene_get_options();

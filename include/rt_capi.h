@@ -176,6 +176,51 @@ int rt_capi_version(void);
  * (rt_render_device), so frames in flight finish on the old scene. */
 int rt_set_scene(rt_ctx* ctx, const rt_prim* prims, int32_t n);
 
+/* ---- lights ------------------------------------------------------------- */
+/* The reference has one white point light at the origin (#define LIGHT_POS point3(0, 0, 0),
+ * main.cpp:14).  rt_set_lights replaces it by 1..RT_MAX_LIGHTS coloured point lights; the
+ * reference's own shading functions take the light as a parameter (diffuse_shading(pos,
+ * normal, light_pos), specular(pos, normal, light_pos, view_dir)).
+ *
+ * n == 0 (lights may be NULL) restores the reference's light: every later call routes and
+ * behaves exactly as on a ctx that never had lights (the plain and shadow kernels, the same
+ * bytes).  1 <= n <= RT_MAX_LIGHTS: the records are copied and apply to every launch enqueued
+ * afterwards; frames already enqueued keep theirs (no synchronisation).  Valid before
+ * rt_set_scene; the lights survive rt_set_scene.  RT_ERR_INVALID_ARG, with the state
+ * unchanged: n < 0 or n > RT_MAX_LIGHTS, NULL lights with n > 0, a non-finite position or
+ * colour component.  Colours are not clamped.
+ *
+ * Shading with lights set, at every accepted hit of recursive_ray_tracing, at every level,
+ * for frames and for ray-batch radiance, with pos, col.normal, mat and the ray direction d as
+ * main.cpp:99-104 has them; lights l = 0..n-1 in order, P_l = position, C_l = color:
+ *   diff_l = diffuse_shading(pos, col.normal, P_l)
+ *   spec_l = pow(specular(pos, col.normal, P_l, -d), mat.specular_exponent)
+ *   s_l    = diff_l * mat.diffuse + spec_l * mat.specular
+ *   with RT_FLAG_SHADOWS: s_l = +0.0 if the segment sp .. P_l is occluded, where
+ *            sp = pos + col.normal * .0001, direction P_l - sp (component-wise), T = 1,
+ *            by rt_occluded's definition (the hit object takes part like any other)
+ *   per channel c:  t = C_l[c] * s_l;   acc[c] = (l == 0) ? t : acc[c] + t
+ *   local[c] = mat.color[c] * (acc[c] + mat.ambient)
+ * All fp64, one IEEE operation per written operation, nothing fused.  Ray paths, the sky, the
+ * metallic lerp and the segment counts are untouched; light rays are not counted.  pos == P_l
+ * or sp == P_l exactly is unspecified.  One light {(0,0,0), (1,1,1)} gives the reference's
+ * bits (1.0 * s is s), and with the flag the bits of RT_FLAG_SHADOWS without lights.
+ *
+ * RT_PREC_F64 follows the definition operation for operation; RT_PREC_PATH64 has the same
+ * fp64 paths and the same fp64 shadow decisions with fp32 colour arithmetic; RT_PREC_MIXED is
+ * served by the F64 kernels.  RT_ERR_UNSUPPORTED, before any launch, while lights are set:
+ * RT_PREC_F32, RT_FLAG_SUN, rt_tile_row_costs.  As for shadowed frames, RT_OPT_PIXEL_PAIRS is
+ * ignored, RT_OPT_FRAME_BATCH launches such frames one at a time and RT_OPT_ROW_FEEDBACK
+ * neither samples nor reorders them; RT_OPT_SUPERSAMPLE, row bands,
+ * rt_render_device_interleaved and rt_multi_* work.  rt_trace_rays* with out == NULL,
+ * rt_occluded* and rt_frame_boxes ignore the lights. */
+#define RT_MAX_LIGHTS 8
+typedef struct rt_light {        /* 48 bytes */
+    double position[3];
+    double color[3];             /* linear RGB factor of the light's contribution, unclamped */
+} rt_light;
+int rt_set_lights(rt_ctx* ctx, const rt_light* lights, int32_t n);
+
 /* ---- tuning ------------------------------------------------------------- */
 enum rt_option {
     RT_OPT_WAVE_CULL_MIN_SPHERES = 1, /* scenes with at least this many spheres use the
@@ -586,6 +631,9 @@ const char* rt_multi_last_error(const rt_multi* m);
  * state: tile boxes, measured row order). */
 int rt_multi_set_scene(rt_multi* m, const rt_prim* prims, int32_t n);
 int rt_multi_set_option(rt_multi* m, int32_t option, int64_t value);
+/* rt_set_lights on every local rank's ctx (every process of a multi-process operator calls it
+ * with the same lights, as rt_multi_set_scene). */
+int rt_multi_set_lights(rt_multi* m, const rt_light* lights, int32_t n);
 
 /* Enqueue one frame.  d_frame: on the process holding the root, DEVICE memory on the root's
  * device of height x width pixels of out_format (the root's band is rendered into it in

@@ -269,6 +269,16 @@ int rt_set_scene(rt_ctx* ctx, const rt_prim* prims, int32_t n) {
     return RT_OK;
 }
 
+/* No device work: the records travel by value in the arguments of every later launch of the
+ * lights kernels, so frames in flight keep the lights they were enqueued with. */
+int rt_set_lights(rt_ctx* ctx, const rt_light* lights, int32_t n) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const int st = pack_lights(lights, n, ctx->lights);  // (leaves ctx->lights alone on failure)
+    if (st != RT_OK) return st;
+    ctx->opt.lights = ctx->lights.n > 0;
+    return RT_OK;
+}
+
 /* Host-only: no ctx, no device. */
 int rt_frame_boxes(const rt_prim* prims, int32_t n, const rt_camera* cam, int32_t row0,
                    int32_t nrows, int16_t* out, int32_t cap, int32_t* nbox, int32_t* mir_depth) {

@@ -133,6 +133,7 @@ struct rt_ctx {
     bool have_scene = false;
     unsigned long long scene_gen = 0;  // bumped by every rt_set_scene
     rth::SceneHost sc;
+    rt::LightArgs lights{};  // rt_set_lights: n == 0 = the reference's light (plain kernels)
     rth::FrameOptions opt;
     rth::BoxCache box_cache;
     rth::RowFeedback rf;
@@ -220,10 +221,11 @@ void feedback_release(rt_ctx* ctx);  // rt_ctx_destroy
 
 int check_render_args(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
                       const FrameReq& rq);
-/* RT_FLAG_SHADOWS (rt_capi.h): the shadow kernels exist for the fp64-path precisions without
- * the sun term; checked before anything is launched. */
-inline int check_shadow_flags(int32_t precision, uint32_t flags) {
-    if (!(flags & RT_FLAG_SHADOWS)) return RT_OK;
+/* RT_FLAG_SHADOWS and scene lights (rt_capi.h): the shadow and lights kernels exist for the
+ * fp64-path precisions without the sun term; checked before anything is launched.  lights: the
+ * ctx has lights set (rt_set_lights). */
+inline int check_shadow_flags(int32_t precision, uint32_t flags, bool lights = false) {
+    if (!(flags & RT_FLAG_SHADOWS) && !lights) return RT_OK;
     if (precision == RT_PREC_F32 || (flags & RT_FLAG_SUN)) return RT_ERR_UNSUPPORTED;
     return RT_OK;
 }

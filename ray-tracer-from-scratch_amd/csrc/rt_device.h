@@ -61,6 +61,9 @@ static_assert(sizeof(DevMat32) == 32, "material layout");
 enum { PREC_F64 = 0, PREC_F32 = 1, PREC_MIXED = 2, PREC_PATH64 = 3 };
 enum { OUT_RGB_F32 = 0, OUT_RGB_F64 = 1, OUT_RGBA8 = 2, OUT_RGBA8_WRAP = 3 };
 enum { FLAG_SUN = 1, FLAG_SHADOWS = 2 };
+// Host-internal bit of KParams::flags (never an rt_capi.h flag): the frame was prepared with
+// scene lights set (rt_set_lights) and launches the lights kernels.
+constexpr uint32_t FLAG_LIGHTS = 0x80000000u;
 
 // Pixel tile of one workgroup: RT_WAVES_PER_BLOCK waves (1, 2 or 4), each an 8x8 square.
 // One wave per workgroup measured fastest (tools/ab.py: c5 -15..21%, c3 -7..12%, c2 -2%
@@ -260,6 +263,30 @@ struct RayArgs {
 int launch_rays(const KParams& p, const RayArgs& ra, int prec, void* stream, void* done_event);
 // The same with FLAG_SHADOWS (rt_rays_shadow.hip): radiance only (ra.shade), no sun.
 int launch_rays_shadow(const KParams& p, const RayArgs& ra, int prec, void* stream, void* done_event);
+
+// Scene lights (rt_set_lights): the records of the lights kernels (rt_trace_lights.hip,
+// rt_rays_lights.hip), which take them by value behind their KParams, so a launch keeps the
+// lights it was enqueued with and no other kernel's arguments change.  Wave-uniform, read
+// through scalar loads.  colf: the colour rounded to fp32 for PATH64's colour arithmetic.
+constexpr int MAX_LIGHTS = 8;
+struct DevLight {
+    double pos[3];
+    double col[3];
+    float colf[3];
+    float pad;
+};
+static_assert(sizeof(DevLight) == 64, "light record layout");
+struct LightArgs {
+    DevLight l[MAX_LIGHTS];
+    int32_t n;  // 1..MAX_LIGHTS in a launch (0 on a ctx without lights: the plain kernels)
+    int32_t pad;
+};
+// A frame / a radiance batch with la.n >= 1 lights: F64 (MIXED is served by it) and PATH64, no
+// sun; FLAG_SHADOWS in p.flags is a wave-uniform runtime branch of the same kernels.  The
+// frame launcher has launch_trace_shadow's conditions otherwise.
+int launch_trace_lights(const KParams& p, const LightArgs& la, int prec, void* stream, void* done_event);
+int launch_rays_lights(const KParams& p, const RayArgs& ra, const LightArgs& la, int prec, void* stream,
+                       void* done_event);
 
 // Occlusion queries (rt_occluded*, rt_rays.hip k_ray_occluded): is anything on the segment
 // o .. o + d * tmax of each caller ray?  Only the scene and cull fields of KParams are used.

@@ -387,7 +387,8 @@ rt::KParams make_params(const FrameScene& fs, BoxCache* bc, const rt_camera* cam
     p.row0 = row0;
     p.nrows = nrows;
     p.depth = rq.depth;
-    p.flags = rq.flags;
+    // (the host-internal bit is never the caller's: other flag bits stay ignored)
+    p.flags = (rq.flags & ~rt::FLAG_LIGHTS) | (opt.lights ? rt::FLAG_LIGHTS : 0u);
     p.outf = rq.out_format;
     for (int k = 0; k < 3; k++) {
         p.pos[k] = cam->position[k];
@@ -398,7 +399,7 @@ rt::KParams make_params(const FrameScene& fs, BoxCache* bc, const rt_camera* cam
     p.out = d_out;
     p.segs = d_segs;
     // (one sample per lane when resolving; no two-pixel shadow kernels)
-    p.pairs = (opt.pixel_pairs && !opt.ss_log2 && !(rq.flags & RT_FLAG_SHADOWS)) ? 1 : 0;
+    p.pairs = (opt.pixel_pairs && !opt.ss_log2 && !(rq.flags & RT_FLAG_SHADOWS) && !opt.lights) ? 1 : 0;
     p.stats = opt.d_stats;
     // eye tables (rt_device.h) for the linear-scan kernels: the same fp64 operations, in
     // the same order, as sphere_exact / wall_exact on a ray starting at cam->position

@@ -3,7 +3,8 @@
  * lane (trace_pair_p64) and in fp32 (trace_pixel_f), band rows, the supersample resolve, a
  * wave's tile, a workgroup of the grid and the frame kernel k_trace.  Not a header of its own:
  * included inside the namespace of a frame unit (rt_trace.hip, rt_trace_stamp.hip,
- * rt_trace_shadow.hip) behind rt_scan_dev.h; the ray units do not include it. */
+ * rt_trace_shadow.hip, rt_trace_lights.hip) behind rt_scan_dev.h; the ray units do not include
+ * it. */
 
 /* Dispatch order of tile rows (workgroup row blockIdx.y -> tile row).  Per-tile cost is
  * very uneven (sky/ground tiles end after one segment, tiles over reflective walls bounce
@@ -213,6 +214,22 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
     auto ld_m = [&](int q) __attribute__((always_inline)) -> int {
         if constexpr (LSTK) return lds_m[q * BLOCK + tid]; else return st_m[q];
     };
+#if RT_LIGHTS
+    // Coloured lights: a level keeps acc[c] + ka per channel (shade_lights_*) instead of the
+    // scalar s.  Three values per level are 6 VGPRs in fp64, so this part of the stack lives
+    // in LDS in every lights kernel ([channel][level][lane], conflict-free as lds_s); the
+    // material slots keep their place (registers where mirror_keep reads them).
+    __shared__ CT lds_l[3 * MAXD * BLOCK];
+    auto push_l = [&](int k, CT vx, CT vy, CT vz, int mv) __attribute__((always_inline)) {
+        lds_l[(0 * MAXD + k) * BLOCK + tid] = vx;
+        lds_l[(1 * MAXD + k) * BLOCK + tid] = vy;
+        lds_l[(2 * MAXD + k) * BLOCK + tid] = vz;
+        if constexpr (LSTK) lds_m[k * BLOCK + tid] = mv; else st_m[k] = mv;
+    };
+    auto ld_l = [&](int c, int q) __attribute__((always_inline)) -> CT {
+        return lds_l[(c * MAXD + q) * BLOCK + tid];
+    };
+#endif
     int n = 0;
     d3 c64 = D3(0, 0, 0);
     f3 c32 = F3(0.f, 0.f, 0.f);
@@ -248,6 +265,11 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
         // counted segment.  A shadowed hit has diffuse = specular = 0: s = 0*kd + 0*ks + ka
         const bool dark = light_blocked<CULL>(p, r, h, alive);
 #endif
+#if RT_LIGHTS
+        // the light rays of every lane that hit (RT_FLAG_SHADOWS: a runtime branch), one
+        // any-hit scan per light while the wave is still converged; bit l = light l is hidden
+        const unsigned dark = lights_blocked<CULL>(p, r, h, alive);
+#endif
         if (!alive) return;
         ++segs;
         if (!COLOR64 && RT_TERMINAL_F32 && (last || h.slot < 0)) {
@@ -266,11 +288,15 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
                     N32 = tof(ld3(p.w64[h.slot - p.nS].n));
                 }
                 const DevMat32& m32 = p.mat32[h.slot];
+#if RT_LIGHTS
+                c32 = mul3(m32.color, shade_lights_f(p, m32, pos, fnormalize(N32), nv32, dark));
+#else
                 const float2 sh = shade_f(m32, tof(pos), fnormalize(N32), nv32, sun);
 #if RT_SHADOW
                 c32 = local_color_f(m32, dark ? m32.ka : sh.x, sh.y, sun);
 #else
                 c32 = local_color_f(m32, sh.x, sh.y, sun);
+#endif
 #endif
             }
             alive = false;
@@ -305,6 +331,26 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
         // cull kernels keep recomputing it (the select costs them 4 VGPRs and a wave/SIMD)
         const d3 nn = (h.slot < p.nS || (MIXED && CULL)) ? normalize_e(N)
                                                            : ld3(p.wnn[h.slot - p.nS]);
+#if RT_LIGHTS
+        // acc[c] + ka per channel; local = color * that, at push and at unwind alike
+        CT vx, vy, vz;
+        if constexpr (COLOR64) {
+            const d3 v = shade_lights_d<INT_EXP>(p, m, pos, nn, -nv, dark);
+            vx = v.x, vy = v.y, vz = v.z;
+        } else {
+            const f3 v = shade_lights_f(p, p.mat32[h.slot], pos, tof(nn), tof(nv), dark);
+            vx = v.x, vy = v.y, vz = v.z;
+        }
+        if (last) {
+            if constexpr (COLOR64)
+                c64 = mul3(m.color, D3(vx, vy, vz));
+            else
+                c32 = mul3(p.mat32[h.slot].color, F3(vx, vy, vz));
+            alive = false;
+            return;
+        }
+        push_l(k, vx, vy, vz, h.slot);
+#else
         CT s, ks;
         if (COLOR64) {
             const ShadeD sh = shade_d<INT_EXP>(m, pos, nn, -nv, sun);
@@ -327,6 +373,7 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
             return;
         }
         push(k, s, ks, h.slot);
+#endif
         n = k + 1;
         // start + reflect(d, N) (main.cpp:111-113, vec.cpp:51-57)
         const double cc = 2 * dot(nv, nn);
@@ -382,6 +429,18 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
         if ((!RT_UNWIND_KEND || q < kend) && q < n) {  // uniform test: levels no lane reached
             const int mq = ld_m(q);
             const DevMat& m = p.mat[mq];
+#if RT_LIGHTS
+            if constexpr (COLOR64) {
+                const d3 L = mul3(m.color, D3(ld_l(0, q), ld_l(1, q), ld_l(2, q)));
+                c64 = lerp(L, c64, m.km);  // vec.cpp:45-49 via main.cpp:117
+            } else {
+                const DevMat32& m32 = p.mat32[mq];
+                const f3 L = mul3(m32.color, F3(ld_l(0, q), ld_l(1, q), ld_l(2, q)));
+                const float km = m32.km;
+                c32 = F3(fmaf(km, c32.x - L.x, L.x), fmaf(km, c32.y - L.y, L.y),
+                         fmaf(km, c32.z - L.z, L.z));
+            }
+#else
             if (COLOR64) {
                 const d3 L = local_color_d(m, ld_s(q), ld_k(q), sun);
                 c64 = lerp(L, c64, m.km);  // vec.cpp:45-49 via main.cpp:117
@@ -392,6 +451,7 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
                 c32 = F3(fmaf(km, c32.x - L.x, L.x), fmaf(km, c32.y - L.y, L.y),
                          fmaf(km, c32.z - L.z, L.z));
             }
+#endif
         }
     }
     STAGE(4);

@@ -73,6 +73,12 @@ struct SceneHost {
  * host copies the per-frame boxes and eye tables use. */
 int pack_scene(const rt_prim* prims, int32_t n, SceneHost& sc);
 
+/* rt_set_lights' host half: the checked records as the lights kernels take them
+ * (rt::LightArgs).  n == 0 gives out.n == 0, the reference's light.  RT_ERR_INVALID_ARG, with
+ * out untouched, for n outside 0..RT_MAX_LIGHTS, null lights with n > 0 or a non-finite
+ * component. */
+int pack_lights(const rt_light* lights, int32_t n, rt::LightArgs& out);
+
 /* ---- rt_frame_args.cpp ---------------------------------------------------------------- */
 
 /* The options a frame's arguments depend on.  Written by rt_set_option between calls;
@@ -88,6 +94,7 @@ struct FrameOptions {
     bool pixel_pairs = RT_PIXEL_PAIRS_DEFAULT;  // RT_OPT_PIXEL_PAIRS
     bool box_cache_on = true;  // RT_OPT_BOX_CACHE
     int ss_log2 = 0;         // RT_OPT_SUPERSAMPLE: S = 2^ss_log2 rays per pixel side
+    bool lights = false;     // rt_set_lights with n > 0: frames carry rt::FLAG_LIGHTS
     unsigned long long* d_stats = nullptr;  // RT_OPT_STATS_DEVICE_PTR (passed on, never read)
 };
 

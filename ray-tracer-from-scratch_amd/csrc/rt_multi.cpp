@@ -1813,6 +1813,15 @@ int rt_multi_set_scene(rt_multi* m, const rt_prim* prims, int32_t n) {
     return RT_OK;
 }
 
+int rt_multi_set_lights(rt_multi* m, const rt_light* lights, int32_t n) {
+    if (!m) return RT_ERR_INVALID_ARG;
+    for (Rank* k : m->r) {
+        const int st = rt_set_lights(k->ctx, lights, n);
+        if (st != RT_OK) return ctx_err(m, k, st, "rt_set_lights");
+    }
+    return RT_OK;
+}
+
 int rt_multi_set_option(rt_multi* m, int32_t option, int64_t value) {
     if (!m) return RT_ERR_INVALID_ARG;
     if (option == RT_OPT_SUPERSAMPLE) {

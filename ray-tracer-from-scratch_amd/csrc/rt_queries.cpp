@@ -53,10 +53,14 @@ int launch_ray_batch(rt_ctx* ctx, const double* d_origins, const double* d_direc
     ra.hits = reinterpret_cast<rt::DevHit*>(d_hits);
     ra.n = (int32_t)n;
     ra.shade = d_out ? 1 : 0;
-    // RT_FLAG_SHADOWS: the shadow kernels (rt_rays_shadow.hip) shade; a hits-only call ignores it
+    // RT_FLAG_SHADOWS: the shadow kernels (rt_rays_shadow.hip) shade; scene lights: the lights
+    // kernels (rt_rays_lights.hip), with or without the flag; a hits-only call ignores both
+    const bool lights = d_out && ctx->lights.n > 0;
     const bool shadows = d_out && (rq.flags & RT_FLAG_SHADOWS);
-    if (shadows && (rq.flags & RT_FLAG_SUN)) return RT_ERR_UNSUPPORTED;
-    const int e = shadows ? rt::launch_rays_shadow(p, ra, prec, hs, done) : rt::launch_rays(p, ra, prec, hs, done);
+    if ((shadows || lights) && (rq.flags & RT_FLAG_SUN)) return RT_ERR_UNSUPPORTED;
+    const int e = lights    ? rt::launch_rays_lights(p, ra, ctx->lights, prec, hs, done)
+                  : shadows ? rt::launch_rays_shadow(p, ra, prec, hs, done)
+                            : rt::launch_rays(p, ra, prec, hs, done);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_rays");
     return RT_OK;
 }
@@ -125,7 +129,7 @@ int rt_trace_rays(rt_ctx* ctx, const double* origins, const double* directions, 
                   rt_hit* hits, int32_t count_segments, rt_stats* stats) {
     const FrameReq rq{depth, precision, flags, out_format};
     int st = check_ray_args(ctx, origins, directions, n, rq, out, hits);
-    if (st == RT_OK && out) st = check_shadow_flags(precision, flags);
+    if (st == RT_OK && out) st = check_shadow_flags(precision, flags, ctx->lights.n > 0);
     if (st != RT_OK) return st;
     if (n == 0) return no_rays(stats);
     DeviceGuard dg(ctx->device);

@@ -12,7 +12,8 @@
  * segment, the first included, is scanned like a frame's unbinned bounce segment.
  *
  * Not a header of its own: included inside the namespace of a ray unit (rt_rays.hip, rt::kry;
- * rt_rays_shadow.hip, rt::krs, with the light ray of RT_FLAG_SHADOWS) behind rt_scan_dev.h. */
+ * rt_rays_shadow.hip, rt::krs, with the light ray of RT_FLAG_SHADOWS; rt_rays_lights.hip,
+ * rt::krl, with the scene lights of rt_set_lights) behind rt_scan_dev.h. */
 #ifndef RT_RAY_STACK_LDS
 #define RT_RAY_STACK_LDS 1
 #endif
@@ -94,6 +95,19 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
     auto ld_m = [&](int q) __attribute__((always_inline)) -> int {
         if constexpr (LSTK) return lds_m[q * BLOCK + tid]; else return st_m[q];
     };
+#if RT_LIGHTS
+    // coloured lights: acc[c] + ka per channel and level, in LDS (trace_pixel_d's lds_l)
+    __shared__ CT lds_l[3 * MAXD * BLOCK];
+    auto push_l = [&](int k, CT vx, CT vy, CT vz, int mv) __attribute__((always_inline)) {
+        lds_l[(0 * MAXD + k) * BLOCK + tid] = vx;
+        lds_l[(1 * MAXD + k) * BLOCK + tid] = vy;
+        lds_l[(2 * MAXD + k) * BLOCK + tid] = vz;
+        if constexpr (LSTK) lds_m[k * BLOCK + tid] = mv; else st_m[k] = mv;
+    };
+    auto ld_l = [&](int c, int q) __attribute__((always_inline)) -> CT {
+        return lds_l[(c * MAXD + q) * BLOCK + tid];
+    };
+#endif
     int n = 0;
     d3 c64 = D3(0, 0, 0);
     f3 c32 = F3(0.f, 0.f, 0.f);
@@ -104,6 +118,10 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
 #if RT_SHADOW
         // the light ray of every lane that hit (trace_pixel_d's step): converged, not counted
         const bool dark = light_blocked<CULL>(p, r, h, alive);
+#endif
+#if RT_LIGHTS
+        // one light ray per light with RT_FLAG_SHADOWS (trace_pixel_d's step): bit l = hidden
+        const unsigned dark = lights_blocked<CULL>(p, r, h, alive);
 #endif
         if (!alive) return;
         ++segs;
@@ -123,11 +141,15 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
                     N32 = tof(ld3(p.w64[h.slot - p.nS].n));
                 }
                 const DevMat32& m32 = p.mat32[h.slot];
+#if RT_LIGHTS
+                c32 = mul3(m32.color, shade_lights_f(p, m32, pos, fnormalize(N32), nv32, dark));
+#else
                 const float2 sh = shade_f(m32, tof(pos), fnormalize(N32), nv32, sun);
 #if RT_SHADOW
                 c32 = local_color_f(m32, dark ? m32.ka : sh.x, sh.y, sun);
 #else
                 c32 = local_color_f(m32, sh.x, sh.y, sun);
+#endif
 #endif
             }
             alive = false;
@@ -159,6 +181,25 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
         const DevMat& m = p.mat[h.slot];
         // normalize(N): a wall's is a scene constant (host, same IEEE operations)
         const d3 nn = h.slot < p.nS ? normalize_e(N) : ld3(p.wnn[h.slot - p.nS]);
+#if RT_LIGHTS
+        CT vx, vy, vz;  // acc[c] + ka per channel (trace_pixel_d)
+        if constexpr (COLOR64) {
+            const d3 v = shade_lights_d<INT_EXP>(p, m, pos, nn, -nv, dark);
+            vx = v.x, vy = v.y, vz = v.z;
+        } else {
+            const f3 v = shade_lights_f(p, p.mat32[h.slot], pos, tof(nn), tof(nv), dark);
+            vx = v.x, vy = v.y, vz = v.z;
+        }
+        if (last) {
+            if constexpr (COLOR64)
+                c64 = mul3(m.color, D3(vx, vy, vz));
+            else
+                c32 = mul3(p.mat32[h.slot].color, F3(vx, vy, vz));
+            alive = false;
+            return;
+        }
+        push_l(k, vx, vy, vz, h.slot);
+#else
         CT s, ks;
         if (COLOR64) {
             const ShadeD sh = shade_d<INT_EXP>(m, pos, nn, -nv, sun);
@@ -181,6 +222,7 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
             return;
         }
         push(k, s, ks, h.slot);
+#endif
         n = k + 1;
         // start + reflect(d, N) (main.cpp:111-113, vec.cpp:51-57)
         const double cc = 2 * dot(nv, nn);
@@ -201,6 +243,18 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
         if (q < kend && q < n) {  // kend: uniform test for the levels no lane reached
             const int mq = ld_m(q);
             const DevMat& m = p.mat[mq];
+#if RT_LIGHTS
+            if constexpr (COLOR64) {
+                const d3 L = mul3(m.color, D3(ld_l(0, q), ld_l(1, q), ld_l(2, q)));
+                c64 = lerp(L, c64, m.km);  // vec.cpp:45-49 via main.cpp:117
+            } else {
+                const DevMat32& m32 = p.mat32[mq];
+                const f3 L = mul3(m32.color, F3(ld_l(0, q), ld_l(1, q), ld_l(2, q)));
+                const float km = m32.km;
+                c32 = F3(fmaf(km, c32.x - L.x, L.x), fmaf(km, c32.y - L.y, L.y),
+                         fmaf(km, c32.z - L.z, L.z));
+            }
+#else
             if (COLOR64) {
                 const d3 L = local_color_d(m, ld_s(q), ld_k(q), sun);
                 c64 = lerp(L, c64, m.km);  // vec.cpp:45-49 via main.cpp:117
@@ -211,6 +265,7 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
                 c32 = F3(fmaf(km, c32.x - L.x, L.x), fmaf(km, c32.y - L.y, L.y),
                          fmaf(km, c32.z - L.z, L.z));
             }
+#endif
         }
     }
     if (COLOR64) return c64;

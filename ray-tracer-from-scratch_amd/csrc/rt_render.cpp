@@ -104,8 +104,13 @@ void prep_main(rt_ctx* ctx) {
     }
 }
 
-/* The frame launch: the shadow kernels (rt_trace_shadow.hip) for a flagged frame. */
-int launch_frame(const rt::KParams& p, int32_t precision, void* stream, void* done_event = nullptr) {
+/* The frame launch: the lights kernels (rt_trace_lights.hip) for a frame prepared while the ctx
+ * had lights set (they take RT_FLAG_SHADOWS at run time), with the ctx's current records; the
+ * shadow kernels (rt_trace_shadow.hip) for a flagged frame without lights. */
+int launch_frame(const rt_ctx* ctx, const rt::KParams& p, int32_t precision, void* stream,
+                 void* done_event = nullptr) {
+    if (p.flags & rt::FLAG_LIGHTS)
+        return rt::launch_trace_lights(p, ctx->lights, precision, stream, done_event);
     if (p.flags & rt::FLAG_SHADOWS) return rt::launch_trace_shadow(p, precision, stream, done_event);
     return rt::launch_trace(p, precision, stream, done_event);
 }
@@ -130,7 +135,7 @@ int launch_prepared(rt_ctx* ctx, const rt::KParams& p, int32_t precision, hipStr
     HP(2);
     // RT_DRY_LAUNCH (diagnostic builds, tools/multi_host_cost.py): every host step of the
     // frame but the kernel launch, to separate the host's own work from the runtime's
-    const int e = RT_DRY_LAUNCH ? (int)hipSuccess : launch_frame(p, precision, hs, done);
+    const int e = RT_DRY_LAUNCH ? (int)hipSuccess : launch_frame(ctx, p, precision, hs, done);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_trace");
     if (RT_DRY_LAUNCH) return RT_OK;
     st = isolate_after(ctx, hs, sampled);
@@ -157,7 +162,7 @@ int render_device_impl(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t 
 #endif
     HP_START();
     int st = check_render_args(ctx, cam, row0, nrows, rq);
-    if (st == RT_OK) st = check_shadow_flags(rq.precision, rq.flags);
+    if (st == RT_OK) st = check_shadow_flags(rq.precision, rq.flags, ctx->lights.n > 0);
     if (st != RT_OK) return st;
     if (!d_out && nrows > 0 && cam->width > 0) return RT_ERR_INVALID_ARG;
     if (ctx->opt.ss_log2 && il) return RT_ERR_UNSUPPORTED;  // contiguous bands only
@@ -262,9 +267,10 @@ int launch_frame_groups(rt_ctx* ctx, const FrameBatch& b, const FrameReq& rq) {
             if (st != RT_OK) break;
             const bool other_grid = n > 0 && (p.W != grp[0].W || p.nrows != grp[0].nrows ||
                                               p.row_units_log2 != grp[0].row_units_log2);
-            // (no table kernels for the cull, pair, supersample and shadow paths: one launch each)
+            // (no table kernels for the cull, pair, supersample, shadow and lights paths: one
+            // launch each)
             if (p.tile_cost || other_grid || p.wave_cull || p.pairs || p.ss_log2 ||
-                (p.flags & rt::FLAG_SHADOWS)) {
+                (p.flags & (rt::FLAG_SHADOWS | rt::FLAG_LIGHTS))) {
                 // this frame alone (after the frames grouped so far), through the per-frame path
                 const rt::KParams one = p;
                 st = launch_group(ctx, s, n, rq.precision, hs);
@@ -415,7 +421,8 @@ int rt_render_device_frames(rt_ctx* ctx, const rt_camera* cams, int32_t ncams, i
     if (!ctx || !cams || ncams <= 0 || !d_outs || nouts <= 0 || nframes < 0 ||
         (nstreams > 0 && !streams) || nstreams < 0)
         return RT_ERR_INVALID_ARG;
-    if (nframes > 0 && check_shadow_flags(precision, flags) != RT_OK) return RT_ERR_UNSUPPORTED;
+    if (nframes > 0 && check_shadow_flags(precision, flags, ctx->lights.n > 0) != RT_OK)
+        return RT_ERR_UNSUPPORTED;
     const FrameReq rq{depth, precision, flags, out_format};
     const FrameBatch b{cams, ncams, row0, nrows, d_outs, nouts, streams, nstreams, nframes};
     // RT_OPT_ROW_MIX 1: consecutive frames on different streams overlap on the GPU
@@ -450,7 +457,7 @@ int rt_render(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows, in
               int32_t count_segments, rt_stats* stats) {
     const FrameReq rq{depth, precision, flags, out_format};
     int st = check_render_args(ctx, cam, row0, nrows, rq);
-    if (st == RT_OK) st = check_shadow_flags(precision, flags);
+    if (st == RT_OK) st = check_shadow_flags(precision, flags, ctx->lights.n > 0);
     if (st != RT_OK) return st;
     const size_t bytes = (size_t)nrows * (size_t)cam->width * (size_t)bytes_per_pixel(out_format);
     if (!out && bytes > 0) return RT_ERR_INVALID_ARG;
@@ -469,7 +476,7 @@ int rt_render(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows, in
     st = prepare_rows(ctx, ctx->stream, p);
     if (st != RT_OK) return st;
     if ((st = staged_begin(ctx, segs)) != RT_OK) return st;
-    const int e = launch_frame(p, precision, ctx->stream);
+    const int e = launch_frame(ctx, p, precision, ctx->stream);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_trace");
     RT_HIP(ctx, hipEventRecord(g.ev1, ctx->stream));
     st = snapshot_costs(ctx, ctx->stream, p);

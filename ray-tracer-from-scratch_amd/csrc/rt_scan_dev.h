@@ -8,7 +8,7 @@
  * thread per pixel) it replaces the reference's rt_scene loop (main.cpp:124-139) and
  * everything under it; rt_rays_dev.h builds the same path for caller rays.
  * Not a header of its own: included inside `namespace rt { namespace <unit> {`, which the
- * including unit opens behind rt_knobs.h.  It depends on RT_STAMP and RT_SHADOW only.
+ * including unit opens behind rt_knobs.h.  It depends on RT_STAMP, RT_SHADOW and RT_LIGHTS only.
  *
  * Precisions (template PREC):
  *   PREC_F64   the reference's fp64 arithmetic.  The units are built with
@@ -1169,6 +1169,97 @@ __device__ __forceinline__ bool light_blocked(const KParams& p, const RayD& r, c
 }
 #endif
 
+#if RT_LIGHTS
+#include "rt_anyhit.h"
+
+/* Scene lights (rt_set_lights, rt_capi.h "Lights").  The lights units rename KParams to their
+ * KParamsL, which carries the light records behind the frame's arguments (p.lights).
+ *
+ * lights_blocked: light_blocked for every light — bit l of the result = the segment from
+ * sp = pos + col.normal * .0001 to light l's position is occluded (direction P_l - sp, T = 1,
+ * rt_occluded's definition).  RT_FLAG_SHADOWS is a wave-uniform runtime branch: without it no
+ * light ray is shot.  pos, N and sp are formed once, in fp64 whatever the caller shades in.
+ * Called converged, as light_blocked. */
+template <bool CULL>
+__device__ __forceinline__ unsigned lights_blocked(const KParams& p, const RayD& r, const HitD& h,
+                                                   bool alive) {
+    if (!(p.flags & FLAG_SHADOWS)) return 0u;  // wave-uniform
+    const bool open = alive && h.slot >= 0;
+    if (!__any(open)) return 0u;  // wave-uniform
+    d3 sp = D3(0.0, 0.0, 1.0);
+    if (open) {
+        const d3 pos = r.o + r.d * h.dist;
+        d3 N;
+        if (h.slot < p.nS) {
+            const double* S = p.s64[h.slot >> 2].v[h.slot & 3];
+            N = (r.o + r.d * h.pt) - D3(S[0], S[1], S[2]);
+        } else {
+            N = ld3(p.w64[h.slot - p.nS].n);
+        }
+        sp = pos + N * .0001;
+    }
+    unsigned dark = 0u;
+    for (int l = 0; l < p.lights.n; ++l) {
+        const d3 P = ld3(p.lights.l[l].pos);
+        const RayD sr = make_ray(sp, D3(P.x - sp.x, P.y - sp.y, P.z - sp.z));
+        bool todo = open;
+        if (CULL)
+            occluded_cull(p, sr, todo, 1.0);
+        else
+            occluded_linear(p, sr, todo, 1.0);
+        dark |= (open && !todo) ? (1u << l) : 0u;
+    }
+    return dark;
+}
+
+/* Shading of one hit under the lights, fp64 (rt_capi.h's formula, one IEEE operation per
+ * written operation): per light diffuse_shading and specular as shade_d forms them with
+ * LIGHT_POS = P_l, s_l = diff*kd + spec*ks (+0.0 where bit l of dark is set), then per channel
+ * acc = C_l * s_l summed in light order.  Returns acc + ka per channel: local = color * that,
+ * the value the recursion stack keeps per level.  One light {(0,0,0), (1,1,1)} gives shade_d's
+ * s in every channel (1.0 * s == s). */
+template <bool INT_EXP>
+__device__ __forceinline__ d3 shade_lights_d(const KParams& p, const DevMat& m, const d3 pos,
+                                             const d3 nn, const d3 view, unsigned dark) {
+    d3 acc = D3(0.0, 0.0, 0.0);
+    for (int l = 0; l < p.lights.n; ++l) {
+        const d3 P = ld3(p.lights.l[l].pos);
+        const d3 ldir = normalize_e(D3(P.x - pos.x, P.y - pos.y, P.z - pos.z));  // P_l - pos
+        const double lamb = dot(ldir, nn);
+        const double diffuse = lamb > 0 ? lamb : 0;
+        double res = dot(normalize_e(view + ldir), nn);
+        res = res > 0 ? res : 0;
+        const double spec = pow_e<INT_EXP>(res, m.ex);
+        double s = diffuse * m.kd + spec * m.ks;
+        if ((dark >> l) & 1u) s = 0.0;
+        const d3 t = ld3(p.lights.l[l].col) * s;
+        acc = l == 0 ? t : acc + t;
+    }
+    return D3(acc.x + m.ka, acc.y + m.ka, acc.z + m.ka);
+}
+/* The same for PATH64's fp32 colour (shade_f's formulas per light).  pos is the exact fp64 hit
+ * position: P_l - pos is formed in fp64 and rounded once, so a light close to a surface costs
+ * no more relative error than a distant one. */
+__device__ __forceinline__ f3 shade_lights_f(const KParams& p, const DevMat32& m, const d3 pos,
+                                             const f3 nn, const f3 nv, unsigned dark) {
+    const float kd = m.kd, ks = m.ks, ex = m.ex;
+    f3 acc = F3(0.f, 0.f, 0.f);
+    for (int l = 0; l < p.lights.n; ++l) {
+        const d3 P = ld3(p.lights.l[l].pos);
+        const f3 ldir = fnormalize(tof(D3(P.x - pos.x, P.y - pos.y, P.z - pos.z)));
+        const float lamb = fmaxf(fdot(ldir, nn), 0.0f);
+        const float res = fmaxf(fdot(fnormalize(ldir - nv), nn), 0.0f);
+        float s = fmaf(lamb, kd, fpow(res, ex) * ks);
+        if ((dark >> l) & 1u) s = 0.0f;
+        const float* C = p.lights.l[l].colf;
+        acc = F3(fmaf(C[0], s, acc.x), fmaf(C[1], s, acc.y), fmaf(C[2], s, acc.z));
+    }
+    return F3(acc.x + m.ka, acc.y + m.ka, acc.z + m.ka);
+}
+__device__ __forceinline__ d3 mul3(const double* c, d3 v) { return D3(c[0] * v.x, c[1] * v.y, c[2] * v.z); }
+__device__ __forceinline__ f3 mul3(const float* c, f3 v) { return F3(c[0] * v.x, c[1] * v.y, c[2] * v.z); }
+#endif
+
 /* ------------------------------------------------------------------------ */
 /* epilogue: pixel store, segment count, occupancy targets                   */
 /* ------------------------------------------------------------------------ */
@@ -1249,6 +1340,18 @@ constexpr int waves_per_eu() {
  * cull kernels spilled 40-300 B per lane (`make asm`), so those run one wave per SIMD lower. */
 template <int PREC, bool CULL, int MAXD>
 constexpr int shadow_waves(int w) {
+#if RT_LIGHTS
+    {  // the lights kernels carry the shadow kernels' state across the light loop: their
+        // targets, capped by what the per-level colour stack in LDS admits (three values and
+        // the material slot per level and lane, one wave per workgroup, 160 KB per CU)
+        // (and one wave less for the shallow fp64-colour cull kernels, which spilled 68 B at 5)
+        const int drop = !CULL ? 1 : ((PREC == PREC_PATH64 ? MAXD < 10 : MAXD < 8) ? 1 : 0);
+        const int lds = MAXD * 64 * (3 * (PREC == PREC_PATH64 ? 4 : 8) + 4);
+        const int cap = (160 * 1024 / lds + 3) / 4;
+        const int t = w - drop < cap ? w - drop : cap;
+        return t < 2 ? 2 : t;
+    }
+#endif
     if (!RT_SHADOW) return w;
     const int drop = !CULL ? 1 : ((PREC == PREC_PATH64 && MAXD < 10) ? 1 : 0);
     return w - drop < 2 ? 2 : w - drop;

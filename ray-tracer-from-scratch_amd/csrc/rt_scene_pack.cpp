@@ -311,4 +311,23 @@ int pack_scene(const rt_prim* prims, int32_t n, SceneHost& sc) {
     return RT_OK;
 }
 
+int pack_lights(const rt_light* lights, int32_t n, rt::LightArgs& out) {
+    static_assert(RT_MAX_LIGHTS == rt::MAX_LIGHTS, "the kernels' light table");
+    if (n < 0 || n > RT_MAX_LIGHTS || (n > 0 && !lights)) return RT_ERR_INVALID_ARG;
+    for (int32_t l = 0; l < n; l++)
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(lights[l].position[k]) || !std::isfinite(lights[l].color[k]))
+                return RT_ERR_INVALID_ARG;
+    rt::LightArgs la{};
+    for (int32_t l = 0; l < n; l++)
+        for (int k = 0; k < 3; k++) {
+            la.l[l].pos[k] = lights[l].position[k];
+            la.l[l].col[k] = lights[l].color[k];
+            la.l[l].colf[k] = (float)lights[l].color[k];
+        }
+    la.n = n;
+    out = la;
+    return RT_OK;
+}
+
 }  // namespace rth

@@ -16,7 +16,7 @@
  *
  *   rt_frames [--frames N] [--keys wwaassdd] [--width W] [--depth D] [--precision f64|mixed|
  *             path64|f32] [--scene default|synthetic:S,W[,seed]] [--ppm file] [--gpu-surface]
- *             [--supersample 1|2|4|8] [--shadows]
+ *             [--supersample 1|2|4|8] [--shadows] [--light x,y,z[,r,g,b]]...
  *
  * --gpu-surface replaces rt_scene + the host packing loop by one rt_render with the
  * kernel's RT_OUT_RGBA8_WRAP epilogue: the same bytes main.cpp:345 produces, highlights
@@ -25,6 +25,9 @@
  * not in the reference: anti-aliased frames), on either path.
  * --shadows sets RT_FLAG_SHADOWS (hard shadows of the point light; not in the reference), on
  * either path; not with --precision f32.
+ * --light x,y,z[,r,g,b] adds a point light (rt_set_lights; colour 1,1,1 when omitted),
+ * repeatable up to RT_MAX_LIGHTS times: the lights given replace the reference's white light at
+ * the origin, on either path; not with --precision f32.
  */
 #include <chrono>
 #include <cmath>
@@ -55,6 +58,7 @@ struct Args {
     bool gpu_surface = false;
     int supersample = 1;
     bool shadows = false;
+    std::vector<RtLight> lights;
 };
 
 int parse_precision(const std::string& s) {
@@ -86,6 +90,17 @@ Args parse(int argc, char** argv) {
         else if (o == "--ppm") a.ppm = val();
         else if (o == "--gpu-surface") a.gpu_surface = true;
         else if (o == "--shadows") a.shadows = true;
+        else if (o == "--light") {
+            double v[6] = {0, 0, 0, 1, 1, 1};
+            const std::string s = val();
+            const int got = std::sscanf(s.c_str(), "%lf,%lf,%lf,%lf,%lf,%lf", &v[0], &v[1], &v[2], &v[3],
+                                        &v[4], &v[5]);
+            if ((got != 3 && got != 6) || a.lights.size() >= RT_MAX_LIGHTS) {
+                std::fprintf(stderr, "--light takes x,y,z[,r,g,b], at most %d times\n", RT_MAX_LIGHTS);
+                std::exit(2);
+            }
+            a.lights.push_back(RtLight{point3(v[0], v[1], v[2]), RGB(v[3], v[4], v[5])});
+        }
         else if (o == "--supersample") {
             a.supersample = std::atoi(val().c_str());
             if (a.supersample != 1 && a.supersample != 2 && a.supersample != 4 && a.supersample != 8) {
@@ -175,6 +190,7 @@ int main(int argc, char** argv) {
     opts.precision = a.precision;
     opts.supersample = a.supersample;
     if (a.shadows) opts.flags |= RT_FLAG_SHADOWS;
+    opts.lights = a.lights;
     rt_scene_set_options(opts);
 
     const int W = a.width, H = (int)cam.image_height;
@@ -192,6 +208,10 @@ int main(int argc, char** argv) {
         for (size_t j = 0; j < scene.size(); j++) scene[j]->pack(&prims[j]);
         if (rt_set_scene(ctx, prims.data(), (int32_t)prims.size()) != RT_OK) return 1;
         if (rt_set_option(ctx, RT_OPT_SUPERSAMPLE, a.supersample) != RT_OK) return 1;
+        std::vector<rt_light> ls;
+        for (const RtLight& l : a.lights)
+            ls.push_back(rt_light{{l.position.x, l.position.y, l.position.z}, {l.color.x, l.color.y, l.color.z}});
+        if (rt_set_lights(ctx, ls.data(), (int32_t)ls.size()) != RT_OK) return 1;
     }
 
     std::vector<int64_t> total_times, rt_times, outpainting_times, shading_times,

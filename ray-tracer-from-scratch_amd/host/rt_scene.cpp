@@ -79,6 +79,16 @@ void check_multi(int st, rt_multi* m, const char* what) {
                                  rt_multi_last_error(m));
 }
 
+/* RtSceneOptions::lights as the C-ABI's records (empty: n == 0, the reference's light). */
+std::vector<rt_light> light_records(const RtSceneOptions& o) {
+    std::vector<rt_light> ls(o.lights.size());
+    for (size_t l = 0; l < ls.size(); l++) {
+        const RtLight& s = o.lights[l];
+        ls[l] = rt_light{{s.position.x, s.position.y, s.position.z}, {s.color.x, s.color.y, s.color.z}};
+    }
+    return ls;
+}
+
 }  // namespace
 
 void rt_scene_shutdown() {
@@ -164,6 +174,13 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
     c.width = W;
     c.height = H;
     g.staging.resize((size_t)W * H * 3);
+    // (no device work: the records travel with every launch)
+    const std::vector<rt_light> ls = light_records(g.opts);
+    if (tiled)
+        check_multi(rt_multi_set_lights(g.multi, ls.data(), (int32_t)ls.size()), g.multi,
+                    "rt_multi_set_lights");
+    else
+        check(rt_set_lights(g.ctx, ls.data(), (int32_t)ls.size()), g.ctx, "rt_set_lights");
     if (tiled)
         check_multi(rt_multi_render(g.multi, &c, g.opts.depth, g.opts.precision, g.opts.flags,
                                     RT_OUT_RGB_F64, g.staging.data(), nullptr),
@@ -272,6 +289,8 @@ std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& 
     std::vector<double> o, d;
     flatten_rays(rays, o, d);
     const int prec = g.opts.precision == RT_PREC_MIXED ? RT_PREC_F64 : g.opts.precision;
+    const std::vector<rt_light> ls = light_records(g.opts);
+    check(rt_set_lights(g.ctx, ls.data(), (int32_t)ls.size()), g.ctx, "rt_set_lights");
     std::vector<double> rgb(rays.size() * 3);
     check(rt_trace_rays(g.ctx, o.data(), d.data(), (int64_t)rays.size(), remaining_iterations, prec,
                         g.opts.flags, RT_OUT_RGB_F64, rgb.data(), nullptr, 0, nullptr),

@@ -80,6 +80,7 @@ RT_OPT_ROW_FEEDBACK_EMA = 14
 RT_OPT_ROW_FEEDBACK_ISOLATE = 15
 RT_OPT_ROW_MIX = 23          # 0 heaviest first, 1 mixed for frames in flight on streams, 2 mixed always
 ROW_PERM_MAX = 2048          # dispatch units of a row order (rt_set_row_order, rt_order_units)
+RT_MAX_LIGHTS = 8            # scene lights of rt_set_lights
 
 
 class rt_material(C.Structure):
@@ -117,6 +118,25 @@ class rt_camera(C.Structure):
     ]
 
 
+class rt_light(C.Structure):
+    """A coloured point light of rt_set_lights (48 bytes)."""
+    _fields_ = [("position", C.c_double * 3), ("color", C.c_double * 3)]
+
+
+def light_array(lights):
+    """lights as a ctypes array of rt_light: rt_light records, or (position, color) pairs of
+    three numbers each.  None or an empty list gives (None, 0): the reference's light."""
+    recs = []
+    for l in lights or []:
+        if not isinstance(l, rt_light):
+            pos, col = l
+            l = rt_light((C.c_double * 3)(*pos), (C.c_double * 3)(*col))
+        recs.append(l)
+    if not recs:
+        return None, 0
+    return (rt_light * len(recs))(*recs), len(recs)
+
+
 class rt_stats(C.Structure):
     _fields_ = [("ms", C.c_double), ("segments", C.c_uint64)]
 
@@ -142,6 +162,7 @@ SIGNATURES = [
     ("rt_last_hip_error", C.c_char_p, [C.c_void_p]),
     ("rt_capi_version", C.c_int, []),
     ("rt_set_scene", C.c_int, [C.c_void_p, C.POINTER(rt_prim), C.c_int32]),
+    ("rt_set_lights", C.c_int, [C.c_void_p, C.POINTER(rt_light), C.c_int32]),
     ("rt_set_option", C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     ("rt_render", C.c_int,
      [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -193,6 +214,7 @@ SIGNATURES = [
     ("rt_multi_last_error", C.c_char_p, [C.c_void_p]),
     ("rt_multi_set_scene", C.c_int, [C.c_void_p, C.POINTER(rt_prim), C.c_int32]),
     ("rt_multi_set_option", C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
+    ("rt_multi_set_lights", C.c_int, [C.c_void_p, C.POINTER(rt_light), C.c_int32]),
     ("rt_multi_render_device", C.c_int,
      [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p,
       C.c_void_p]),
@@ -403,6 +425,13 @@ class Renderer:
         arr = (rt_prim * len(prims))(*prims)
         self._prims = arr
         check(self.lib.rt_set_scene(self.ctx, arr, len(prims)), self.ctx)
+
+    def set_lights(self, lights) -> None:
+        """rt_set_lights: 1..RT_MAX_LIGHTS coloured point lights (rt_light records or
+        (position, color) pairs) for every launch enqueued afterwards; None or [] restores the
+        reference's white light at the origin."""
+        arr, n = light_array(lights)
+        check(self.lib.rt_set_lights(self.ctx, arr, n), self.ctx)
 
     def set_option(self, option: int, value: int) -> None:
         check(self.lib.rt_set_option(self.ctx, option, value), self.ctx)
@@ -625,6 +654,11 @@ class MultiRenderer:
         arr = (rt_prim * max(1, len(prims)))(*prims)
         self._prims = arr
         self._check(self.lib.rt_multi_set_scene(self.m, arr, len(prims)))
+
+    def set_lights(self, lights) -> None:
+        """rt_multi_set_lights: Renderer.set_lights on every local rank."""
+        arr, n = light_array(lights)
+        self._check(self.lib.rt_multi_set_lights(self.m, arr, n))
 
     def set_option(self, option: int, value: int) -> None:
         self._check(self.lib.rt_multi_set_option(self.m, option, value))

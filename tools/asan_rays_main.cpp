@@ -4,11 +4,12 @@
 // runtime).  It packs scenes through the host-only rt_frame_boxes (pack_scene: spheres,
 // walls, an interleaved order, a wall with a NaN basis), orders dispatch units through the
 // host-only rt_order_units (rt_row_order.cpp), walks the argument checks of
-// rt_trace_rays, rt_trace_rays_device and rt_occluded*, and converts hit records to
-// Collisions.  Where a HIP device exists it also runs the entry points on a small batch; without one
+// rt_trace_rays, rt_trace_rays_device, rt_occluded* and rt_set_lights, and converts hit records
+// to Collisions.  Where a HIP device exists it also runs the entry points on a small batch; without one
 // rt_ctx_create returns RT_ERR_NO_DEVICE and the device part is skipped (and said so).
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -119,6 +120,11 @@ int main() {
     EXPECT(rt_occluded(nullptr, o, d, tmax, 2, occ, &nocc, &st) == RT_ERR_INVALID_ARG);
     EXPECT(rt_occluded_device(nullptr, o, d, tmax, 2, occ, &nocc, nullptr) == RT_ERR_INVALID_ARG);
     EXPECT(occ[0] == 7 && occ[1] == 7 && nocc == 9);
+    rt_light lights[RT_MAX_LIGHTS + 1] = {};
+    for (rt_light& l : lights) l.color[0] = l.color[1] = l.color[2] = 0.25;
+    EXPECT(rt_set_lights(nullptr, lights, 1) == RT_ERR_INVALID_ARG);
+    EXPECT(rt_multi_set_lights(nullptr, lights, 1) == RT_ERR_INVALID_ARG);
+    EXPECT(sizeof(rt_light) == 48);
 
     // hit records -> Collision
     rt_hit h{};
@@ -162,6 +168,20 @@ int main() {
             EXPECT(rt_occluded(ctx, o, d, tmax, 2, occ, &nocc, &st) == RT_OK);
             EXPECT(occ[0] == 1 && nocc == (uint64_t)(occ[0] + occ[1]) && st.segments == 2);
             EXPECT(rt_occluded(ctx, o, d, nullptr, 2, occ, nullptr, nullptr) == RT_OK && occ[0] == 1);
+            // rt_set_lights: the refused arguments, the full table, back to the reference's light
+            EXPECT(rt_set_lights(ctx, lights, RT_MAX_LIGHTS + 1) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_set_lights(ctx, lights, -1) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_set_lights(ctx, nullptr, 1) == RT_ERR_INVALID_ARG);
+            lights[3].position[1] = std::nan("");
+            EXPECT(rt_set_lights(ctx, lights, 4) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_set_lights(ctx, lights, 3) == RT_OK);
+            lights[3].position[1] = 0;
+            EXPECT(rt_set_lights(ctx, lights, RT_MAX_LIGHTS) == RT_OK);
+            EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, RT_FLAG_SHADOWS, RT_OUT_RGB_F64, rgb, hits, 1,
+                                 &st) == RT_OK);
+            EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, RT_FLAG_SUN, RT_OUT_RGB_F64, rgb, hits, 1,
+                                 &st) == RT_ERR_UNSUPPORTED);
+            EXPECT(rt_set_lights(ctx, nullptr, 0) == RT_OK);
             rt_ctx_destroy(ctx);
         }
     }
