@@ -201,6 +201,22 @@ std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& 
 std::vector<unsigned char> rt_occluded(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
                                        const std::vector<ray>& rays,
                                        const std::vector<double>& tmax = {});
+/* A frame's AOVs (rt_render_aov, include/rt_capi.h) over the same renderer: what the primary
+ * ray of every pixel of rt_scene's frame hits, row-major, pixel (row i, column j) at
+ * i * width + j.
+ *   hits[k]    == find_closest_hit(scene, the pixel's ray of main.cpp:132-134)
+ *   depth[k]   the world distance camera .. hit (a wall's t * |d|; +inf for a miss)
+ *   normal, albedo   three floats per pixel: the normalised hit normal, the hit object's
+ *                    mat.color; zeros for a miss
+ * u, cam: rt_scene's arguments (Camera::init's pixel deltas and the camera).  A SceneGeometry
+ * subclass without a GPU record throws std::invalid_argument, as above. */
+struct RtAov {
+    int width = 0, height = 0;
+    std::vector<Collision> hits;
+    std::vector<float> depth, normal, albedo;
+};
+RtAov rt_scene_aov(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                   const Camera& cam);
 /* One rt_hit record (rt_trace_rays through the C-ABI directly) as the reference's Collision. */
 Collision rt_collision_from_hit(const rt_hit& h);
 

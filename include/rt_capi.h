@@ -546,6 +546,61 @@ int rt_occluded_device(rt_ctx* ctx, const double* d_origins, const double* d_dir
                        const double* d_tmax, int64_t n, uint8_t* d_out, uint64_t* d_count,
                        void* stream);
 
+/* ---- frame AOVs (the G-buffer of a frame's primary hits) ------------------------------ */
+/* What a frame's PRIMARY rays hit, as per-pixel layers: the hit record, object index, depth,
+ * surface normal and base colour that picking, outlines, compositing, depth cues and denoisers
+ * want next to the colour.  Only the primary segment runs: no shading, no bounce, no lights.
+ *
+ * Pixel (row i, column j) of rows [row0, row0 + nrows) traces the ray of main.cpp:132-134:
+ * origin o = cam.position, direction d = cam.position - ((image_top_left + pixel_delta_x * j)
+ * + pixel_delta_y * i), NOT normalised.  With c = find_closest_hit(scene, ray(d, o))
+ * (main.cpp:67-84) the layers are defined in fp64, one IEEE operation per written operation,
+ * nothing fused; a float layer is that fp64 value converted with one round-to-nearest cast:
+ *   hit     c as an rt_hit: the bytes rt_trace_rays(out = NULL) gives for that ray; a miss is
+ *           {DBL_MAX, {0,0,0}, -1, 0}
+ *   index   c.hit_object_index (rt_set_scene order), -1 = miss
+ *   depth   the WORLD distance from the camera to the hit: c.distance for a sphere (already
+ *           projection * |d|), c.distance * d.length() for a wall (vec.cpp:3-9:
+ *           sqrt(x*x + y*y + z*z), summed left to right), +inf for a miss.  Unlike
+ *           rt_hit.distance (world distance for spheres, parametric t for walls: the
+ *           reference's quirk) one buffer is comparable across kinds.
+ *   normal  c.normal.normalize() (vec.cpp:21-24: each component divided by sqrt(n.n)); a
+ *           wall's is its stored normal divided by its own length again; (0,0,0) for a miss
+ *   albedo  mat.color of the hit object; (0,0,0) for a miss
+ * There is no precision argument, no flags and no depth: the answer is exact.  Buffers are
+ * band-relative, row-major, nrows * width pixels, as for rt_render; a NULL layer is not written
+ * and costs no stores; nothing outside the buffers is written.
+ *
+ * RT_ERR_INVALID_ARG for a NULL ctx, cam or buffers struct, for all five layers NULL or a
+ * non-NULL `reserved`; RT_ERR_NO_SCENE before rt_set_scene; the band checks and their statuses
+ * are rt_render's for the same cam, row0 and nrows.  All before any launch.  An empty scene is
+ * valid: all misses.
+ * Ignored: rt_set_lights, RT_OPT_SUPERSAMPLE (for the samples' AOVs pass
+ * rt_supersample_camera's camera), RT_OPT_PIXEL_PAIRS, RT_OPT_FRAME_BATCH.  RT_OPT_TILE_BINS,
+ * RT_OPT_EYE_TABLES, RT_OPT_WALL_ORDER, RT_OPT_WAVE_CULL_MIN_SPHERES and RT_OPT_CLUSTER_COS
+ * serve the scan; the output is identical for every setting of them.  RT_OPT_ROW_FEEDBACK
+ * neither samples nor reorders an AOV launch, and an AOV call leaves the feedback state, any
+ * measured order and the box cache as they were: a following rt_render* gives the bytes and
+ * launches it would have given without it. */
+typedef struct rt_aov_buffers {  /* 48 bytes; a NULL layer is not written */
+    rt_hit*  hit;      /* nrows*width records           (40 B/px) */
+    int32_t* index;    /* nrows*width                   ( 4 B/px) */
+    float*   depth;    /* nrows*width                   ( 4 B/px) */
+    float*   normal;   /* nrows*width*3, row-major xyz  (12 B/px) */
+    float*   albedo;   /* nrows*width*3                 (12 B/px) */
+    void*    reserved; /* must be NULL */
+} rt_aov_buffers;
+
+/* rt_render_aov: the layers in HOST memory, synchronous (staging buffers in the ctx, like
+ * rt_trace_rays); stats->ms = device time of the kernel, stats->segments = nrows * width. */
+int rt_render_aov(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
+                  const rt_aov_buffers* out, rt_stats* stats);
+/* The same with the layers in DEVICE memory (the struct itself on the host), enqueued on
+ * `stream` (NULL = the ctx's) without synchronising.  Like rt_render_device the launch signals
+ * the ctx's per-stream event that rt_set_scene and rt_ctx_destroy wait on. */
+int rt_render_aov_device(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
+                         const rt_aov_buffers* d_out, void* stream);
+
 /* ---- multi-GPU frame operator (BASELINE config 4) ----------------------- */
 /* ONE frame split into contiguous row bands (rt_band_rows) over nranks ranks, one GPU each,
  * every band rendered by that rank's own rt_ctx, then gathered into the frame buffer of

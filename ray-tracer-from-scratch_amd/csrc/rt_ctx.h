@@ -5,6 +5,7 @@
  *   rt_feedback.cpp  the row feedback's device bookkeeping (RowFeedback)
  *   rt_render.cpp    the frame entry points, the helper thread, the frame table
  *   rt_queries.cpp   ray batches and occlusion queries
+ *   rt_aov.cpp       frame AOVs (the primary hits' layers)
  *
  * A ctx belongs to one caller thread at a time (rt_capi.h).  The only other thread is
  * rt_render.cpp's helper (RT_OPT_HOST_PIPELINE), alive inside rt_render_device_frames: it
@@ -136,6 +137,7 @@ struct rt_ctx {
     rt::LightArgs lights{};  // rt_set_lights: n == 0 = the reference's light (plain kernels)
     rth::FrameOptions opt;
     rth::BoxCache box_cache;
+    rth::BoxCache aov_box_cache;  // rt_render_aov*'s own (rt_aov.cpp): the frames' stays as it was
     rth::RowFeedback rf;
     rth::FrameTable tab;
     rth::Staging stg;

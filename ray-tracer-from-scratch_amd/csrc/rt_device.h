@@ -300,6 +300,19 @@ struct OccArgs {
 };
 int launch_occluded(const KParams& p, const OccArgs& oa, void* stream, void* done_event);
 
+// Frame AOVs (rt_render_aov*, rt_trace_aov.hip k_aov): the primary segment of the frame p
+// describes (camera, band, eye tables, wall order, primary boxes; one 8x8 tile per wave like the
+// frame kernels), its hit written as per-pixel layers, band-relative and row-major.  The layer
+// pointers travel by value behind the KParams; a null layer is not written (wave-uniform).
+struct AovArgs {
+    DevHit* hit;     // [nrows * W] find_closest_hit's record (k_ray_hits' bytes)
+    int32_t* index;  // [nrows * W] scene index, -1 = miss
+    float* depth;    // [nrows * W] world distance camera .. hit, +inf = miss
+    float* normal;   // [nrows * W][3] normalize(record normal), 0 = miss
+    float* albedo;   // [nrows * W][3] the hit material's colour, 0 = miss
+};
+int launch_aov(const KParams& p, const AovArgs& a, void* stream, void* done_event);
+
 // Device self-test of the exact fp64 helpers against IEEE operations:
 // which 0 = division (shared reciprocal), 1 = integer-exponent pow vs pow(),
 // 2 = sqrt_e vs sqrt(); adds the number of mismatches (division, sqrt: bitwise;

@@ -16,7 +16,7 @@
  *
  *   rt_frames [--frames N] [--keys wwaassdd] [--width W] [--depth D] [--precision f64|mixed|
  *             path64|f32] [--scene default|synthetic:S,W[,seed]] [--ppm file] [--gpu-surface]
- *             [--supersample 1|2|4|8] [--shadows] [--light x,y,z[,r,g,b]]...
+ *             [--supersample 1|2|4|8] [--shadows] [--light x,y,z[,r,g,b]]... [--aov PREFIX]
  *
  * --gpu-surface replaces rt_scene + the host packing loop by one rt_render with the
  * kernel's RT_OUT_RGBA8_WRAP epilogue: the same bytes main.cpp:345 produces, highlights
@@ -28,6 +28,9 @@
  * --light x,y,z[,r,g,b] adds a point light (rt_set_lights; colour 1,1,1 when omitted),
  * repeatable up to RT_MAX_LIGHTS times: the lights given replace the reference's white light at
  * the origin, on either path; not with --precision f32.
+ * --aov PREFIX writes the first frame's G-buffer layers (rt_scene_aov; not in the reference)
+ * as raw row-major files: PREFIX.depth.f32 (world distance of the primary hit, +inf = miss) and
+ * PREFIX.index.i32 (scene index, -1 = miss), image_height x width values each.
  */
 #include <chrono>
 #include <cmath>
@@ -59,6 +62,7 @@ struct Args {
     int supersample = 1;
     bool shadows = false;
     std::vector<RtLight> lights;
+    std::string aov;
 };
 
 int parse_precision(const std::string& s) {
@@ -90,6 +94,7 @@ Args parse(int argc, char** argv) {
         else if (o == "--ppm") a.ppm = val();
         else if (o == "--gpu-surface") a.gpu_surface = true;
         else if (o == "--shadows") a.shadows = true;
+        else if (o == "--aov") a.aov = val();
         else if (o == "--light") {
             double v[6] = {0, 0, 0, 1, 1, 1};
             const std::string s = val();
@@ -162,6 +167,13 @@ void build_scene(const std::string& spec, std::vector<std::unique_ptr<SceneGeome
  * outside the int32 range give INT32_MIN) and the low byte — in-range values truncate,
  * highlights above 1.0 wrap modulo 256 (1.084 displays as 20).  Written without the
  * undefined conversion so any compiler gives those bytes. */
+bool write_raw(const std::string& path, const void* data, size_t bytes) {
+    FILE* fp = std::fopen(path.c_str(), "wb");
+    if (!fp) return false;
+    const bool ok = std::fwrite(data, 1, bytes, fp) == bytes;
+    return std::fclose(fp) == 0 && ok;
+}
+
 inline uint8_t to_u8(double v) {
     const double t = v * 255;
     const int32_t i = (t > -2147483649.0 && t < 2147483648.0) ? (int32_t)t : INT32_MIN;
@@ -225,6 +237,16 @@ int main(int argc, char** argv) {
                 case 'a': cam.left(); break;
                 case 'd': cam.right(); break;
                 default: break;
+            }
+        }
+        if (f == 0 && !a.aov.empty()) {  // the first frame's depth and index layers
+            const RtAov g = rt_scene_aov(u, scene, cam);
+            std::vector<int32_t> index(g.hits.size());
+            for (size_t k = 0; k < index.size(); k++) index[k] = g.hits[k].hit_object_index;
+            if (!write_raw(a.aov + ".depth.f32", g.depth.data(), g.depth.size() * sizeof(float)) ||
+                !write_raw(a.aov + ".index.i32", index.data(), index.size() * sizeof(int32_t))) {
+                std::fprintf(stderr, "cannot write %s.*\n", a.aov.c_str());
+                return 1;
             }
         }
         const auto rt_start_time = clk::now();

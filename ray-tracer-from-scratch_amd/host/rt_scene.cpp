@@ -89,6 +89,22 @@ std::vector<rt_light> light_records(const RtSceneOptions& o) {
     return ls;
 }
 
+/* The frame's camera as the C-ABI takes it: position and image_top_left of cam, the pixel
+ * deltas Camera::init returned (u), the frame size (main.cpp:124-134). */
+rt_camera camera_record(const std::vector<vec3>& u, const Camera& cam) {
+    rt_camera c{};
+    const vec3* v[4] = {&cam.position, &cam.image_top_left, &u.at(0), &u.at(1)};
+    double* dst[4] = {c.position, c.image_top_left, c.pixel_delta_x, c.pixel_delta_y};
+    for (int k = 0; k < 4; k++) {
+        dst[k][0] = v[k]->x;
+        dst[k][1] = v[k]->y;
+        dst[k][2] = v[k]->z;
+    }
+    c.width = (int)cam.image_width;
+    c.height = (int)cam.image_height;
+    return c;
+}
+
 }  // namespace
 
 void rt_scene_shutdown() {
@@ -162,17 +178,8 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
         if (!tiled) g.ctx_prims = prims;
     }
 
-    rt_camera c{};
-    const vec3* v[4] = {&cam.position, &cam.image_top_left, &u.at(0), &u.at(1)};
-    double* dst[4] = {c.position, c.image_top_left, c.pixel_delta_x, c.pixel_delta_y};
-    for (int k = 0; k < 4; k++) {
-        dst[k][0] = v[k]->x;
-        dst[k][1] = v[k]->y;
-        dst[k][2] = v[k]->z;
-    }
-    const int W = (int)cam.image_width, H = (int)cam.image_height;
-    c.width = W;
-    c.height = H;
+    const rt_camera c = camera_record(u, cam);
+    const int W = c.width, H = c.height;
     g.staging.resize((size_t)W * H * 3);
     // (no device work: the records travel with every launch)
     const std::vector<rt_light> ls = light_records(g.opts);
@@ -279,6 +286,32 @@ std::vector<unsigned char> rt_occluded(const std::vector<std::unique_ptr<SceneGe
                       (int64_t)rays.size(), out.data(), nullptr, nullptr),
           g.ctx, "rt_occluded");
     return out;
+}
+
+RtAov rt_scene_aov(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                   const Camera& cam) {
+    Global& g = global();
+    std::lock_guard<std::mutex> lk(g.mu);
+    ray_scene(g, scene);
+    const rt_camera c = camera_record(u, cam);
+    RtAov a;
+    a.width = c.width;
+    a.height = c.height;
+    const size_t n = (size_t)(c.width > 0 ? c.width : 0) * (size_t)(c.height > 0 ? c.height : 0);
+    if (n == 0) return a;
+    std::vector<rt_hit> hits(n);
+    a.depth.resize(n);
+    a.normal.resize(n * 3);
+    a.albedo.resize(n * 3);
+    rt_aov_buffers b{};
+    b.hit = hits.data();
+    b.depth = a.depth.data();
+    b.normal = a.normal.data();
+    b.albedo = a.albedo.data();
+    check(rt_render_aov(g.ctx, &c, 0, c.height, &b, nullptr), g.ctx, "rt_render_aov");
+    a.hits.reserve(n);
+    for (const rt_hit& h : hits) a.hits.push_back(rt_collision_from_hit(h));
+    return a;
 }
 
 std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& scene,

@@ -153,6 +153,17 @@ HIT_DTYPE = np.dtype([("distance", np.float64), ("normal", np.float64, (3,)),
                       ("index", np.int32), ("reserved", np.int32)])
 
 
+class rt_aov_buffers(C.Structure):
+    """The layers of rt_render_aov* (48 bytes); a NULL layer is not written."""
+    _fields_ = [("hit", C.c_void_p), ("index", C.c_void_p), ("depth", C.c_void_p),
+                ("normal", C.c_void_p), ("albedo", C.c_void_p), ("reserved", C.c_void_p)]
+
+
+# the layers of a frame's AOVs: name -> (dtype, trailing shape), in rt_aov_buffers' order
+AOV_LAYERS = {"hit": (HIT_DTYPE, ()), "index": (np.int32, ()), "depth": (np.float32, ()),
+              "normal": (np.float32, (3,)), "albedo": (np.float32, (3,))}
+
+
 # Every entry point include/rt_capi.h declares: (name, restype, argtypes).
 _dbl3 = C.POINTER(C.c_double)
 SIGNATURES = [
@@ -204,6 +215,13 @@ SIGNATURES = [
       C.POINTER(rt_stats)]),
     ("rt_occluded_device", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+      C.c_void_p]),
+    # frame AOVs
+    ("rt_render_aov", C.c_int,
+     [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.POINTER(rt_aov_buffers),
+      C.POINTER(rt_stats)]),
+    ("rt_render_aov_device", C.c_int,
+     [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.POINTER(rt_aov_buffers),
       C.c_void_p]),
     # multi-GPU frame operator
     ("rt_multi_unique_id", C.c_int, [C.POINTER(C.c_uint8)]),
@@ -587,6 +605,37 @@ class Renderer:
             self.ctx, C.c_void_p(d_origins or None), C.c_void_p(d_directions or None),
             C.c_void_p(d_tmax or None), n, C.c_void_p(d_out or None), C.c_void_p(d_count or None),
             C.c_void_p(stream or None)), self.ctx)
+
+    def render_aov(self, cam: rt_camera, layers=("hit", "index", "depth", "normal", "albedo"),
+                   row0: int = 0, nrows: int | None = None):
+        """rt_render_aov: the primary hits of rows [row0, row0 + nrows) of cam's frame as
+        per-pixel layers, synchronous -> ({layer: array}, stats).  hit is a HIT_DTYPE array
+        [nrows, width], index int32 and depth float32 [nrows, width], normal and albedo
+        float32 [nrows, width, 3]."""
+        if nrows is None:
+            nrows = cam.height - row0
+        out = {}
+        for name in layers:
+            dt, tail = AOV_LAYERS[name]
+            out[name] = np.empty((nrows, cam.width) + tail, dt)
+        bufs = rt_aov_buffers(**{k: v.ctypes.data for k, v in out.items()})
+        st = rt_stats()
+        check(self.lib.rt_render_aov(self.ctx, C.byref(cam), row0, nrows, C.byref(bufs),
+                                     C.byref(st)), self.ctx)
+        return out, st
+
+    def render_aov_device(self, cam: rt_camera, d_layers: dict, row0: int = 0,
+                          nrows: int | None = None, stream: int = 0) -> None:
+        """rt_render_aov_device: the same into raw device addresses ({layer: address}; a layer
+        left out or 0 is not written), enqueued on `stream` without synchronising."""
+        if nrows is None:
+            nrows = cam.height - row0
+        unknown = set(d_layers) - set(AOV_LAYERS)
+        if unknown:
+            raise ValueError(f"unknown AOV layers {sorted(unknown)}")
+        bufs = rt_aov_buffers(**{k: (v or None) for k, v in d_layers.items()})
+        check(self.lib.rt_render_aov_device(self.ctx, C.byref(cam), row0, nrows, C.byref(bufs),
+                                            C.c_void_p(stream or None)), self.ctx)
 
 
 def multi_unique_id() -> bytes:

@@ -4,8 +4,8 @@
 // runtime).  It packs scenes through the host-only rt_frame_boxes (pack_scene: spheres,
 // walls, an interleaved order, a wall with a NaN basis), orders dispatch units through the
 // host-only rt_order_units (rt_row_order.cpp), walks the argument checks of
-// rt_trace_rays, rt_trace_rays_device, rt_occluded* and rt_set_lights, and converts hit records
-// to Collisions.  Where a HIP device exists it also runs the entry points on a small batch; without one
+// rt_trace_rays, rt_trace_rays_device, rt_occluded*, rt_render_aov* and rt_set_lights, and
+// converts hit records to Collisions.  Where a HIP device exists it also runs the entry points on a small batch; without one
 // rt_ctx_create returns RT_ERR_NO_DEVICE and the device part is skipped (and said so).
 #include <algorithm>
 #include <cfloat>
@@ -125,6 +125,16 @@ int main() {
     EXPECT(rt_set_lights(nullptr, lights, 1) == RT_ERR_INVALID_ARG);
     EXPECT(rt_multi_set_lights(nullptr, lights, 1) == RT_ERR_INVALID_ARG);
     EXPECT(sizeof(rt_light) == 48);
+    // frame AOVs: what is refused before the ctx is looked at, the buffers untouched
+    EXPECT(sizeof(rt_aov_buffers) == 48);
+    int32_t aov_index[2] = {7, 7};
+    float aov_depth[2] = {7.f, 7.f};
+    rt_aov_buffers ab{};
+    ab.index = aov_index;
+    ab.depth = aov_depth;
+    EXPECT(rt_render_aov(nullptr, &c, 0, 1, &ab, &st) == RT_ERR_INVALID_ARG);
+    EXPECT(rt_render_aov_device(nullptr, &c, 0, 1, &ab, nullptr) == RT_ERR_INVALID_ARG);
+    EXPECT(aov_index[0] == 7 && aov_index[1] == 7 && aov_depth[0] == 7.f && aov_depth[1] == 7.f);
 
     // hit records -> Collision
     rt_hit h{};
@@ -149,6 +159,8 @@ int main() {
         if (cs == RT_OK) {
             EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, 0, RT_OUT_RGB_F64, rgb, hits, 1, &st) ==
                    RT_ERR_NO_SCENE);
+            EXPECT(rt_render_aov(ctx, &c, 0, 1, &ab, &st) == RT_ERR_NO_SCENE);
+            EXPECT(rt_render_aov_device(ctx, &c, 0, 1, &ab, nullptr) == RT_ERR_NO_SCENE);
             EXPECT(rt_set_scene(ctx, prims.data(), (int32_t)prims.size()) == RT_OK);
             EXPECT(rt_trace_rays(ctx, nullptr, d, 2, 4, RT_PREC_F64, 0, RT_OUT_RGB_F64, rgb, hits, 1, &st) ==
                    RT_ERR_INVALID_ARG);
@@ -182,6 +194,24 @@ int main() {
             EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, RT_FLAG_SUN, RT_OUT_RGB_F64, rgb, hits, 1,
                                  &st) == RT_ERR_UNSUPPORTED);
             EXPECT(rt_set_lights(ctx, nullptr, 0) == RT_OK);
+            // rt_render_aov: the refused arguments (statuses before any launch), then one row
+            const rt_aov_buffers none{};
+            rt_aov_buffers bad = ab;
+            bad.reserved = aov_index;
+            EXPECT(rt_render_aov(ctx, nullptr, 0, 1, &ab, &st) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_render_aov(ctx, &c, 0, 1, nullptr, &st) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_render_aov(ctx, &c, 0, 1, &none, &st) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_render_aov(ctx, &c, 0, 1, &bad, &st) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_render_aov_device(ctx, &c, 0, 1, &bad, nullptr) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_render_aov(ctx, &c, -1, 1, &ab, &st) == RT_ERR_OUT_OF_RANGE);
+            EXPECT(rt_render_aov(ctx, &c, c.height, 1, &ab, &st) == RT_ERR_OUT_OF_RANGE);
+            EXPECT(rt_render_aov(ctx, &c, 0, -1, &ab, &st) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_render_aov(ctx, &c, 0, 0, &ab, &st) == RT_OK && aov_index[0] == 7 && st.segments == 0);
+            std::vector<int32_t> row_index(c.width, 7);
+            rt_aov_buffers row{};
+            row.index = row_index.data();
+            EXPECT(rt_render_aov(ctx, &c, c.height / 2, 1, &row, &st) == RT_OK);
+            EXPECT(st.segments == (uint64_t)c.width && row_index[0] != 7);
             rt_ctx_destroy(ctx);
         }
     }
@@ -201,6 +231,13 @@ int main() {
     threw = false;
     try {
         rt_occluded(scene, {ray(vec3(1, 0, 0), point3(0, 0, 0))}, {1.0});
+    } catch (const std::invalid_argument&) {
+        threw = true;
+    }
+    EXPECT(threw);
+    threw = false;
+    try {
+        rt_scene_aov(cam.init(), scene, cam);
     } catch (const std::invalid_argument&) {
         threw = true;
     }
