@@ -217,6 +217,23 @@ struct RtAov {
 };
 RtAov rt_scene_aov(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeometry>>& scene,
                    const Camera& cam);
+/* A frame's ambient occlusion (rt_render_ao, include/rt_capi.h) over the same renderer: at the
+ * primary hit of every pixel of rt_scene's frame, one any-hit probe per direction of `dirs`
+ * (1..RT_AO_MAX_DIRS vectors, not normalised, flipped onto the hemisphere above the surface)
+ * with the parametric limit `radius` (> 0, infinity allowed).  Row-major, pixel (row i, column j)
+ * at i * width + j: count = the occluded probes, ao = the open fraction (1 = nothing near, and
+ * for a miss).  u, cam: rt_scene's arguments.  Invalid directions or radius throw
+ * std::runtime_error with the C-ABI's status; a SceneGeometry subclass without a GPU record
+ * throws std::invalid_argument, as above. */
+struct RtAo {
+    int width = 0, height = 0;
+    std::vector<uint8_t> count;
+    std::vector<float> ao;
+};
+RtAo rt_scene_ao(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                 const Camera& cam, const std::vector<vec3>& dirs, double radius);
+/* rt_ao_directions as vectors: n unit vectors of a spherical Fibonacci set (1 <= n <= 64). */
+std::vector<vec3> rt_ao_direction_set(int n);
 /* One rt_hit record (rt_trace_rays through the C-ABI directly) as the reference's Collision. */
 Collision rt_collision_from_hit(const rt_hit& h);
 

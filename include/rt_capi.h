@@ -601,6 +601,85 @@ int rt_render_aov(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows
 int rt_render_aov_device(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
                          const rt_aov_buffers* d_out, void* stream);
 
+/* ---- ambient occlusion (hemisphere probes at a frame's primary hits) ------------------- */
+/* The reference's ambient term is a constant (mat.ambient), so creases, contacts and corners are
+ * flat.  Ambient occlusion probes the hemisphere above each pixel's primary hit with short
+ * any-hit segments and reports how many are blocked: a geometry layer for compositing and
+ * denoisers, next to rt_render_aov's depth, normal and albedo.  One launch: the primary segment
+ * of rt_render_aov, then the probes of rt_occluded, no ray buffer in between.
+ *
+ * Everything is fp64, one IEEE operation per written operation, nothing fused, dot products
+ * x*x' + y*y' + z*z' summed left to right.  Pixel (row i, column j) has the primary ray (o, d)
+ * of main.cpp:132-134 and c = find_closest_hit(scene, ray(d, o)): rt_render_aov's record.
+ *   miss      count = 0.
+ *   P         the TRUE point the pixel sees: o + d * c.distance for a wall; o + d * projection
+ *             for a sphere (scene.cpp:75's intersection_point, the value c.normal + centre came
+ *             from).  Deliberately not main.cpp:99's pos, which for |d| != 1 uses a sphere's
+ *             world distance as a parameter and lands off the surface: the beauty frame keeps
+ *             that quirk, a geometry layer must not (as the depth AOV is not rt_hit.distance).
+ *             A tangent hit (det == 0 exactly) is unspecified.
+ *   nf        the facing normal: n = c.normal, un-normalised as the record carries it;
+ *             f = dot(d, n); nf = (f > 0) ? -n : n — a wall seen from behind is probed on the
+ *             viewer's side.
+ *   sp        the probes' origin, P + nf * .0001 (the reference's own offset, main.cpp:111).
+ *   probe k   (0 <= k < ndirs) w_k = the caller's direction k; s = dot(w_k, nf);
+ *             w = (s < 0) ? -w_k : w_k (s == 0 is not flipped).  The probe is occluded iff the
+ *             segment sp .. sp + w * radius is occluded by rt_occluded's definition
+ *             (c.distance > 0, parameter <= T = radius); the hit object takes part like any other.
+ *   count     the number of occluded probes, 0..ndirs.
+ *   ao        (float)((double)(ndirs - count) / (double)ndirs): the open fraction, 1.0f for a
+ *             miss and where nothing is near.
+ * Directions are NOT normalised: |w_k| scales what radius means, as |d| does for rt_occluded's
+ * tmax; with unit directions the radius is a world distance.  There is no precision argument,
+ * no flags and no depth: the answer is exact.  Buffers are band-relative, row-major, nrows *
+ * width pixels, as for rt_render; a NULL layer is not written; nothing outside them is written.
+ *
+ * RT_ERR_INVALID_ARG for a NULL ctx, cam, params or buffers struct; both layers NULL; a non-NULL
+ * or non-zero reserved field; dirs == NULL; ndirs outside 1..RT_AO_MAX_DIRS; a direction with a
+ * non-finite component or all three zero; radius NaN or <= 0 (+inf is allowed).
+ * RT_ERR_NO_SCENE before rt_set_scene; the band checks and their statuses are rt_render's for the
+ * same cam, row0 and nrows.  All before any launch, the buffers untouched.  nrows == 0 is RT_OK:
+ * nothing is launched and stats = {0, 0}.  An empty scene is valid: all misses.
+ * Ignored, and left alone, exactly as by rt_render_aov: rt_set_lights, RT_OPT_SUPERSAMPLE,
+ * RT_OPT_PIXEL_PAIRS, RT_OPT_FRAME_BATCH are ignored; RT_OPT_TILE_BINS, RT_OPT_EYE_TABLES,
+ * RT_OPT_WALL_ORDER, RT_OPT_WAVE_CULL_MIN_SPHERES and RT_OPT_CLUSTER_COS serve the scans with
+ * identical output; RT_OPT_ROW_FEEDBACK neither samples nor reorders the launch, and the call
+ * leaves the feedback state, any measured order and the box cache as they were. */
+#define RT_AO_MAX_DIRS 64
+typedef struct rt_ao_params {      /* 32 bytes */
+    const double* dirs;            /* ndirs x 3 doubles, row-major, HOST memory in BOTH entry points */
+    int32_t ndirs;                 /* 1..RT_AO_MAX_DIRS */
+    int32_t reserved;              /* must be 0 */
+    double  radius;                /* the limit T of every probe (a PARAMETER along the probe's
+                                      direction, as rt_occluded's tmax): > 0, +inf allowed */
+    void*   reserved2;             /* must be NULL */
+} rt_ao_params;
+typedef struct rt_ao_buffers {     /* 24 bytes; a NULL layer is not written */
+    uint8_t* count;                /* nrows*width: occluded probes of the pixel, 0..ndirs */
+    float*   ao;                   /* nrows*width: open fraction, 1 = nothing near */
+    void*    reserved;             /* must be NULL */
+} rt_ao_buffers;
+
+/* rt_render_ao: the layers in HOST memory, synchronous (staging buffers in the ctx, like
+ * rt_render_aov); stats->ms = device time of the kernel, stats->segments = nrows * width (probes
+ * are not counted, as shadow rays are not). */
+int rt_render_ao(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
+                 const rt_ao_params* params, const rt_ao_buffers* out, rt_stats* stats);
+/* The same with the layers in DEVICE memory, enqueued on `stream` (NULL = the ctx's) without
+ * synchronising.  Both structs and dirs are HOST memory and are consumed before the call
+ * returns (the directions travel in the kernel's arguments): the caller may overwrite or free
+ * them at once, and a later call with other directions does not change a launch already
+ * enqueued.  Like rt_render_device the launch signals the ctx's per-stream event that
+ * rt_set_scene and rt_ctx_destroy wait on. */
+int rt_render_ao_device(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
+                        const rt_ao_params* params, const rt_ao_buffers* d_out, void* stream);
+/* A default direction set (host only, no ctx): for 1 <= n <= RT_AO_MAX_DIRS, n unit vectors of a
+ * spherical Fibonacci set over the WHOLE sphere — z_k = 1 - (2k+1)/n, r = sqrt(1 - z*z),
+ * phi = k * pi * (3 - sqrt(5)), vector (r cos phi, r sin phi, z) — which the flip folds onto each
+ * pixel's hemisphere.  out: n x 3 doubles.  RT_ERR_INVALID_ARG otherwise.  Its bits depend on the
+ * platform's libm. */
+int rt_ao_directions(int32_t n, double* out);
+
 /* ---- multi-GPU frame operator (BASELINE config 4) ----------------------- */
 /* ONE frame split into contiguous row bands (rt_band_rows) over nranks ranks, one GPU each,
  * every band rendered by that rank's own rt_ctx, then gathered into the frame buffer of

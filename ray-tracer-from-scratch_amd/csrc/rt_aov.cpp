@@ -30,14 +30,7 @@ int check_aov_args(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_
 /* The launch of one band (nrows, width > 0, arguments checked, the ctx's device current). */
 int launch_aov_band(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows,
                     const rt_aov_buffers& d, hipStream_t hs, hipEvent_t done) {
-    FrameOptions opt = ctx->opt;
-    opt.ss_log2 = 0;
-    opt.lights = false;
-    opt.pixel_pairs = false;
-    opt.mirror_bins = false;  // the primary boxes only
-    const FrameReq rq{0, RT_PREC_F64, 0u, RT_OUT_RGB_F32};
-    const rt::KParams p = make_params(FrameScene{ctx->sc, opt, ctx->d_scene, ctx->scene_gen},
-                                      &ctx->aov_box_cache, cam, row0, nrows, rq, nullptr, nullptr);
+    const rt::KParams p = primary_params(ctx, cam, row0, nrows);
     rt::AovArgs a{};
     a.hit = reinterpret_cast<rt::DevHit*>(d.hit);
     a.index = d.index;
@@ -50,6 +43,21 @@ int launch_aov_band(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nro
 }
 
 }  // namespace
+
+namespace rth {
+
+rt::KParams primary_params(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows) {
+    FrameOptions opt = ctx->opt;
+    opt.ss_log2 = 0;
+    opt.lights = false;
+    opt.pixel_pairs = false;
+    opt.mirror_bins = false;  // the primary boxes only
+    const FrameReq rq{0, RT_PREC_F64, 0u, RT_OUT_RGB_F32};
+    return make_params(FrameScene{ctx->sc, opt, ctx->d_scene, ctx->scene_gen}, &ctx->aov_box_cache, cam,
+                       row0, nrows, rq, nullptr, nullptr);
+}
+
+}  // namespace rth
 
 extern "C" {
 

@@ -6,6 +6,7 @@
  *   rt_render.cpp    the frame entry points, the helper thread, the frame table
  *   rt_queries.cpp   ray batches and occlusion queries
  *   rt_aov.cpp       frame AOVs (the primary hits' layers)
+ *   rt_ao.cpp        ambient occlusion frames (probes at the primary hits)
  *
  * A ctx belongs to one caller thread at a time (rt_capi.h).  The only other thread is
  * rt_render.cpp's helper (RT_OPT_HOST_PIPELINE), alive inside rt_render_device_frames: it
@@ -137,7 +138,8 @@ struct rt_ctx {
     rt::LightArgs lights{};  // rt_set_lights: n == 0 = the reference's light (plain kernels)
     rth::FrameOptions opt;
     rth::BoxCache box_cache;
-    rth::BoxCache aov_box_cache;  // rt_render_aov*'s own (rt_aov.cpp): the frames' stays as it was
+    rth::BoxCache aov_box_cache;  // rt_render_aov* / rt_render_ao*'s own (rt_aov.cpp primary_params):
+                                  // the colour frames' stays as it was
     rth::RowFeedback rf;
     rth::FrameTable tab;
     rth::Staging stg;
@@ -233,6 +235,14 @@ inline int check_shadow_flags(int32_t precision, uint32_t flags, bool lights = f
 }
 void render_shutdown(rt_ctx* ctx);       // rt_ctx_destroy, first: joins the helper thread
 void frame_table_release(rt_ctx* ctx);   // rt_ctx_destroy, with nothing in flight
+
+/* ---- rt_aov.cpp ----------------------------------------------------------------------- */
+
+/* The kernel arguments of a frame's PRIMARY segment alone (rt_render_aov*, rt_render_ao*): the
+ * camera, the band, eye tables, wall order, primary pixel boxes and cull choice of make_params,
+ * with the options that have no meaning there switched off (supersampling, lights, pixel pairs,
+ * mirror chains), through the ctx's aov_box_cache.  Nothing of the row feedback takes part. */
+rt::KParams primary_params(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows);
 
 }  // namespace rth
 

@@ -313,6 +313,21 @@ struct AovArgs {
 };
 int launch_aov(const KParams& p, const AovArgs& a, void* stream, void* done_event);
 
+// Ambient occlusion frames (rt_render_ao*, rt_trace_ao.hip k_ao): k_aov's primary segment of the
+// frame p describes, then ndirs any-hit probes at every hit.  The probe directions travel by
+// value behind the KParams, so a launch keeps the directions it was enqueued with; they are
+// wave-uniform and read through scalar loads.  A null layer is not written (wave-uniform).
+constexpr int AO_MAX_DIRS = 64;  // == RT_AO_MAX_DIRS (rt_capi.h)
+struct AoArgs {
+    uint8_t* count;  // [nrows * W] occluded probes of the pixel, 0 = miss
+    float* ao;       // [nrows * W] (ndirs - count) / ndirs, 1 = miss
+    double radius;   // the probes' parametric limit, > 0 (+inf allowed)
+    int32_t ndirs;   // 1..AO_MAX_DIRS
+    int32_t pad;
+    double dirs[AO_MAX_DIRS][3];  // the caller's directions, not normalised
+};
+int launch_ao(const KParams& p, const AoArgs& a, void* stream, void* done_event);
+
 // Device self-test of the exact fp64 helpers against IEEE operations:
 // which 0 = division (shared reciprocal), 1 = integer-exponent pow vs pow(),
 // 2 = sqrt_e vs sqrt(); adds the number of mismatches (division, sqrt: bitwise;

@@ -419,6 +419,13 @@ struct Cone {
     bool on;
 };
 
+/* RT_CONE_AXIS_CHECK (default 0; 1 in rt_trace_ao.hip only): wave_cone rejects a non-finite
+ * axis.  The sum of the live lanes' unit directions is exactly 0 when they cancel in pairs —
+ * impossible to arrange with pixel rays, the rule with rt_render_ao's probes, which are +w_k in
+ * some lanes and -w_k in the others. */
+#ifndef RT_CONE_AXIS_CHECK
+#define RT_CONE_AXIS_CHECK 0
+#endif
 __device__ __forceinline__ Cone wave_cone(f3 o, f3 d, bool alive) {
     Cone c;
     const float inf = __builtin_inff();
@@ -434,6 +441,12 @@ __device__ __forceinline__ Cone wave_cone(f3 o, f3 d, bool alive) {
     const f3 su = F3(uni(wsum(dn.x)), uni(wsum(dn.y)), uni(wsum(dn.z)));
     c.u = fnormalize(su);
     c.cos_t = uni(wmin(alive ? fdot(c.u, dn) : 1.0f)) - 1e-4f;
+#if RT_CONE_AXIS_CHECK
+    // live directions that cancel exactly (w and -w) leave su == 0 and a NaN axis; the dead
+    // lanes' 1.0 then survives the minimum (fminf drops a NaN) and the cone would claim to be
+    // narrow around a NaN axis, culling every sphere and wall: no cone instead
+    if (!(fmax3abs(c.u.x, c.u.y, c.u.z) <= 2.0f)) c.cos_t = -1.0f;
+#endif
     c.sin_t = fsqrt(fmaxf(0.0f, 1.0f - c.cos_t * c.cos_t));
     c.on = c.cos_t > 0.05f;  // a near-hemispherical fan culls nothing: skip the pass
     return c;
@@ -925,6 +938,16 @@ __device__ __forceinline__ int clu_bit(const Clu32& B, int oct, int c) {
  * clu_oinf (100 x the extent, margin 1e-3 x the extent) the widened box still contains the
  * balls' slabs.  d_axis = 0: NaN plane terms drop out of the min / max (no constraint),
  * which is conservative. */
+/* RT_CLU_SLAB_FMA (default RT_CLU_FAST; 0 in rt_trace_ao.hip only): 1 = the fma form.  With a
+ * direction component that is EXACTLY 0 and an origin off 0 on that axis, o/d = +-inf, and
+ * fma(lo, +-inf, -+inf) is -+inf for one plane of a box that straddles 0 and NaN for the other:
+ * the box is rejected although the ray may run through it (not conservative, unlike the NaN
+ * case above).  Pixel and bounce rays do not have exact zeros; a caller's ray may, and so may
+ * the probe directions of rt_render_ao (rt_ao_directions' first vector has y == 0), whose unit
+ * forms (lo - o) * (1/d) instead. */
+#ifndef RT_CLU_SLAB_FMA
+#define RT_CLU_SLAB_FMA RT_CLU_FAST
+#endif
 struct SlabRay {
     f3 o, inv, oi;  // origin, 1/d, o/d (fma form)
 };
@@ -937,7 +960,7 @@ __device__ __forceinline__ SlabRay slab_ray(const f3 o, const f3 d) {
 }
 __device__ __forceinline__ void slab_tt(const Clu32& B, const SlabRay& s, float& tn, float& tf) {
     float x1, x2, y1, y2, z1, z2;
-    if (RT_CLU_FAST) {
+    if (RT_CLU_SLAB_FMA) {
         x1 = fmaf(B.lo[0], s.inv.x, -s.oi.x), x2 = fmaf(B.hi[0], s.inv.x, -s.oi.x);
         y1 = fmaf(B.lo[1], s.inv.y, -s.oi.y), y2 = fmaf(B.hi[1], s.inv.y, -s.oi.y);
         z1 = fmaf(B.lo[2], s.inv.z, -s.oi.z), z2 = fmaf(B.hi[2], s.inv.z, -s.oi.z);

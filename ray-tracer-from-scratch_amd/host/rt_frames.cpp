@@ -17,6 +17,7 @@
  *   rt_frames [--frames N] [--keys wwaassdd] [--width W] [--depth D] [--precision f64|mixed|
  *             path64|f32] [--scene default|synthetic:S,W[,seed]] [--ppm file] [--gpu-surface]
  *             [--supersample 1|2|4|8] [--shadows] [--light x,y,z[,r,g,b]]... [--aov PREFIX]
+ *             [--ao PREFIX [--ao-dirs K] [--ao-radius R]]
  *
  * --gpu-surface replaces rt_scene + the host packing loop by one rt_render with the
  * kernel's RT_OUT_RGBA8_WRAP epilogue: the same bytes main.cpp:345 produces, highlights
@@ -31,6 +32,10 @@
  * --aov PREFIX writes the first frame's G-buffer layers (rt_scene_aov; not in the reference)
  * as raw row-major files: PREFIX.depth.f32 (world distance of the primary hit, +inf = miss) and
  * PREFIX.index.i32 (scene index, -1 = miss), image_height x width values each.
+ * --ao PREFIX writes the first frame's ambient occlusion (rt_scene_ao; not in the reference) the
+ * same way: PREFIX.ao.f32 (open fraction of the hemisphere above the primary hit, 1 = nothing
+ * near) and PREFIX.count.u8 (occluded probes), for --ao-dirs K directions of
+ * rt_ao_direction_set (default 16) and the probe limit --ao-radius R (default inf).
  */
 #include <chrono>
 #include <cmath>
@@ -63,6 +68,9 @@ struct Args {
     bool shadows = false;
     std::vector<RtLight> lights;
     std::string aov;
+    std::string ao;
+    int ao_dirs = 16;
+    double ao_radius = INFINITY;
 };
 
 int parse_precision(const std::string& s) {
@@ -95,6 +103,9 @@ Args parse(int argc, char** argv) {
         else if (o == "--gpu-surface") a.gpu_surface = true;
         else if (o == "--shadows") a.shadows = true;
         else if (o == "--aov") a.aov = val();
+        else if (o == "--ao") a.ao = val();
+        else if (o == "--ao-dirs") a.ao_dirs = std::atoi(val().c_str());
+        else if (o == "--ao-radius") a.ao_radius = std::atof(val().c_str());
         else if (o == "--light") {
             double v[6] = {0, 0, 0, 1, 1, 1};
             const std::string s = val();
@@ -246,6 +257,14 @@ int main(int argc, char** argv) {
             if (!write_raw(a.aov + ".depth.f32", g.depth.data(), g.depth.size() * sizeof(float)) ||
                 !write_raw(a.aov + ".index.i32", index.data(), index.size() * sizeof(int32_t))) {
                 std::fprintf(stderr, "cannot write %s.*\n", a.aov.c_str());
+                return 1;
+            }
+        }
+        if (f == 0 && !a.ao.empty()) {  // the first frame's ambient occlusion layers
+            const RtAo g = rt_scene_ao(u, scene, cam, rt_ao_direction_set(a.ao_dirs), a.ao_radius);
+            if (!write_raw(a.ao + ".ao.f32", g.ao.data(), g.ao.size() * sizeof(float)) ||
+                !write_raw(a.ao + ".count.u8", g.count.data(), g.count.size())) {
+                std::fprintf(stderr, "cannot write %s.*\n", a.ao.c_str());
                 return 1;
             }
         }

@@ -314,6 +314,52 @@ RtAov rt_scene_aov(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneG
     return a;
 }
 
+RtAo rt_scene_ao(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeometry>>& scene,
+                 const Camera& cam, const std::vector<vec3>& dirs, double radius) {
+    Global& g = global();
+    std::lock_guard<std::mutex> lk(g.mu);
+    ray_scene(g, scene);
+    const rt_camera c = camera_record(u, cam);
+    RtAo a;
+    a.width = c.width;
+    a.height = c.height;
+    const size_t n = (size_t)(c.width > 0 ? c.width : 0) * (size_t)(c.height > 0 ? c.height : 0);
+    std::vector<double> w;
+    w.reserve(dirs.size() * 3);
+    for (const vec3& v : dirs) {
+        w.push_back(v.x);
+        w.push_back(v.y);
+        w.push_back(v.z);
+    }
+    a.count.resize(n);
+    a.ao.resize(n);
+    rt_ao_params q{};
+    q.dirs = w.data();
+    q.ndirs = dirs.size() > (size_t)RT_AO_MAX_DIRS ? RT_AO_MAX_DIRS + 1 : (int32_t)dirs.size();
+    q.radius = radius;
+    rt_ao_buffers b{};
+    b.count = a.count.data();
+    b.ao = a.ao.data();
+    // (an empty frame still has its arguments checked: the buffers are not read then)
+    uint8_t none_c = 0;
+    float none_a = 0;
+    if (n == 0) {
+        b.count = &none_c;
+        b.ao = &none_a;
+    }
+    check(rt_render_ao(g.ctx, &c, 0, c.height > 0 ? c.height : 0, &q, &b, nullptr), g.ctx, "rt_render_ao");
+    return a;
+}
+
+std::vector<vec3> rt_ao_direction_set(int n) {
+    std::vector<double> w(n > 0 ? (size_t)n * 3 : 0);
+    check(rt_ao_directions(n, w.data()), nullptr, "rt_ao_directions");
+    std::vector<vec3> out;
+    out.reserve((size_t)n);
+    for (int k = 0; k < n; k++) out.emplace_back(w[3 * k], w[3 * k + 1], w[3 * k + 2]);
+    return out;
+}
+
 std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& scene,
                              const std::vector<ray>& rays, int remaining_iterations) {
     Global& g = global();

@@ -164,6 +164,24 @@ AOV_LAYERS = {"hit": (HIT_DTYPE, ()), "index": (np.int32, ()), "depth": (np.floa
               "normal": (np.float32, (3,)), "albedo": (np.float32, (3,))}
 
 
+RT_AO_MAX_DIRS = 64
+
+
+class rt_ao_params(C.Structure):
+    """The probes of rt_render_ao* (32 bytes): ndirs directions in HOST memory and the limit."""
+    _fields_ = [("dirs", C.POINTER(C.c_double)), ("ndirs", C.c_int32), ("reserved", C.c_int32),
+                ("radius", C.c_double), ("reserved2", C.c_void_p)]
+
+
+class rt_ao_buffers(C.Structure):
+    """The layers of rt_render_ao* (24 bytes); a NULL layer is not written."""
+    _fields_ = [("count", C.c_void_p), ("ao", C.c_void_p), ("reserved", C.c_void_p)]
+
+
+# the layers of an ambient occlusion frame: name -> dtype, in rt_ao_buffers' order
+AO_LAYERS = {"count": np.uint8, "ao": np.float32}
+
+
 # Every entry point include/rt_capi.h declares: (name, restype, argtypes).
 _dbl3 = C.POINTER(C.c_double)
 SIGNATURES = [
@@ -223,6 +241,14 @@ SIGNATURES = [
     ("rt_render_aov_device", C.c_int,
      [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.POINTER(rt_aov_buffers),
       C.c_void_p]),
+    # ambient occlusion
+    ("rt_render_ao", C.c_int,
+     [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.POINTER(rt_ao_params),
+      C.POINTER(rt_ao_buffers), C.POINTER(rt_stats)]),
+    ("rt_render_ao_device", C.c_int,
+     [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.POINTER(rt_ao_params),
+      C.POINTER(rt_ao_buffers), C.c_void_p]),
+    ("rt_ao_directions", C.c_int, [C.c_int32, _dbl3]),
     # multi-GPU frame operator
     ("rt_multi_unique_id", C.c_int, [C.POINTER(C.c_uint8)]),
     ("rt_multi_create", C.c_int,
@@ -636,6 +662,53 @@ class Renderer:
         bufs = rt_aov_buffers(**{k: (v or None) for k, v in d_layers.items()})
         check(self.lib.rt_render_aov_device(self.ctx, C.byref(cam), row0, nrows, C.byref(bufs),
                                             C.c_void_p(stream or None)), self.ctx)
+
+    @staticmethod
+    def _ao_params(dirs, radius: float):
+        """(rt_ao_params, the array it points into) for [k, 3] directions."""
+        w = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+        return rt_ao_params(w.ctypes.data_as(_dbl3), w.shape[0], 0, float(radius), None), w
+
+    def render_ao(self, cam: rt_camera, dirs=None, ndirs: int = 16, radius: float = float("inf"),
+                  layers=("count", "ao"), row0: int = 0, nrows: int | None = None):
+        """rt_render_ao: ambient occlusion of rows [row0, row0 + nrows) of cam's frame,
+        synchronous -> ({layer: array}, stats).  dirs: [k, 3] probe directions (not normalised;
+        None = ao_directions(ndirs)); radius: the probes' parametric limit.  count is uint8
+        [nrows, width] (occluded probes), ao float32 [nrows, width] (open fraction)."""
+        if nrows is None:
+            nrows = cam.height - row0
+        if dirs is None:
+            dirs = ao_directions(ndirs)
+        prm, keep = self._ao_params(dirs, radius)
+        out = {name: np.empty((nrows, cam.width), AO_LAYERS[name]) for name in layers}
+        bufs = rt_ao_buffers(**{k: v.ctypes.data for k, v in out.items()})
+        st = rt_stats()
+        check(self.lib.rt_render_ao(self.ctx, C.byref(cam), row0, nrows, C.byref(prm),
+                                    C.byref(bufs), C.byref(st)), self.ctx)
+        return out, st
+
+    def render_ao_device(self, cam: rt_camera, dirs, radius: float, d_layers: dict, row0: int = 0,
+                         nrows: int | None = None, stream: int = 0) -> None:
+        """rt_render_ao_device: the same into raw device addresses ({layer: address}; a layer
+        left out or 0 is not written), enqueued on `stream` without synchronising.  dirs is
+        host memory, consumed before the call returns."""
+        if nrows is None:
+            nrows = cam.height - row0
+        unknown = set(d_layers) - set(AO_LAYERS)
+        if unknown:
+            raise ValueError(f"unknown AO layers {sorted(unknown)}")
+        prm, keep = self._ao_params(dirs, radius)
+        bufs = rt_ao_buffers(**{k: (v or None) for k, v in d_layers.items()})
+        check(self.lib.rt_render_ao_device(self.ctx, C.byref(cam), row0, nrows, C.byref(prm),
+                                           C.byref(bufs), C.c_void_p(stream or None)), self.ctx)
+
+
+def ao_directions(n: int) -> np.ndarray:
+    """rt_ao_directions: n unit vectors of a spherical Fibonacci set over the whole sphere,
+    [n, 3] float64 (1 <= n <= RT_AO_MAX_DIRS)."""
+    out = np.empty((max(int(n), 0), 3), np.float64)
+    check(load().rt_ao_directions(int(n), out.ctypes.data_as(_dbl3)))
+    return out
 
 
 def multi_unique_id() -> bytes:
