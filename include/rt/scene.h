@@ -153,10 +153,20 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
  * each a position and a colour factor; not with RT_PREC_F32 or RT_FLAG_SUN).  Empty (the
  * default) means the reference's light, LIGHT_POS = (0,0,0), white.  rt_scene — the row-tiled
  * `devices` path included — and rt_radiance honour them; rt_closest_hits and rt_occluded
- * ignore them. */
+ * ignore them.
+ * `transmission`: one record per scene object, in the scene vector's order
+ * (rt_set_transmission, rt_capi.h "Transmission": transmission in [0, 1], 0 = opaque; ior in
+ * [1, 4], read for spheres; not with RT_PREC_F32 or RT_FLAG_SUN).  Empty (the default) means
+ * none; any other size than the scene's makes rt_scene and rt_radiance throw.  rt_scene — the
+ * row-tiled `devices` path included — and rt_radiance honour the records; rt_closest_hits,
+ * rt_occluded, rt_scene_aov and rt_scene_ao ignore them. */
 struct RtLight {
     point3 position;
     RGB color;
+};
+struct RtTransmission {
+    double transmission = 0.0;
+    double ior = 1.0;
 };
 struct RtSceneOptions {
     int device = 0;
@@ -167,6 +177,7 @@ struct RtSceneOptions {
     int transport = RT_TRANSPORT_RCCL;
     int supersample = 1;
     std::vector<RtLight> lights;
+    std::vector<RtTransmission> transmission;
 };
 void rt_scene_set_options(const RtSceneOptions& opts);
 RtSceneOptions rt_scene_get_options();

@@ -221,6 +221,63 @@ typedef struct rt_light {        /* 48 bytes */
 } rt_light;
 int rt_set_lights(rt_ctx* ctx, const rt_light* lights, int32_t n);
 
+/* ---- transmission -------------------------------------------------------- */
+/* Material::metallic hands part of a surface's colour to the reflected ray; a transmission
+ * record hands it to a ray that goes THROUGH the object instead: a wall is a thin pane, a
+ * sphere a solid ball of glass.  One record per scene object, in rt_set_scene's order.
+ *
+ * n is the current scene's object count or 0.  n == 0 (recs may be NULL) clears the records,
+ * and so does a set whose every `transmission` is exactly 0: every later call routes and
+ * behaves exactly as on a ctx that never had records (the same kernels, the same bytes).
+ * rt_set_scene clears them too: they belong to the objects.  A set applies to every launch
+ * enqueued afterwards; launches already enqueued keep theirs (no synchronisation).
+ * RT_ERR_NO_SCENE: n > 0 before a scene is set.  RT_ERR_INVALID_ARG, with the state unchanged:
+ * n neither the scene's count nor 0, NULL recs with n > 0, a non-finite field, transmission
+ * outside [0, 1], ior outside [1, 4].
+ *
+ * Shading, at every accepted hit of recursive_ray_tracing on an object whose tau =
+ * transmission > 0, at every level, for frames and for ray-batch radiance; o, d, col and mat as
+ * main.cpp:91-104 has them.  `local` is computed exactly as without records (lights and
+ * RT_FLAG_SHADOWS included; transmissive objects block light rays like any other) and is
+ * returned when remaining_iterations <= 0.  Otherwise the next ray (o', d') replaces
+ * main.cpp:111-113's reflected ray and the result is, per channel,
+ *   local + tau * (traced(o', d', remaining - 1) - local)
+ * vec.cpp:45-49's lerp with tau in metallic's place; the object's metallic is not used there.
+ * All fp64, one IEEE operation per written operation, nothing fused; dot(u, v) = u.x*v.x +
+ * u.y*v.y + u.z*v.z summed left to right.
+ *
+ * Wall (a thin pane), pos = main.cpp:99's point, n = col.normal:
+ *   f = dot(d, n);  nf = (f > 0) ? -n : n;  o' = pos - nf * .0001;  d' = d (the same bits)
+ *
+ * Sphere with centre c and ior.  P = o + d * projection is scene.cpp:75's intersection point
+ * (rt_render_ao's P), not main.cpp:99's pos:
+ *   n = P - c;  dl = sqrt(dot(d, d));  dh = d / dl;  nl = sqrt(dot(n, n));  nh = n / nl
+ *   ci = -dot(dh, nh);  eta = 1.0 / ior;  k = 1.0 - (eta * eta) * (1.0 - ci * ci)
+ *   t = dh * eta + nh * (eta * ci - sqrt(k))                              (refracted in)
+ *   m = c - P;  s = (2.0 * dot(t, m)) / dot(t, t);  Q = P + t * s         (the chord)
+ *   n2 = Q - c;  l2 = sqrt(dot(n2, n2));  n2h = n2 / l2;  tl = sqrt(dot(t, t));  th = t / tl
+ *   c2 = dot(th, n2h);  k2 = 1.0 - (ior * ior) * (1.0 - c2 * c2);  k2c = (k2 > 0) ? k2 : 0.0
+ *   d' = th * ior + n2h * (sqrt(k2c) - ior * c2);  o' = Q + n2 * .0001    (refracted out)
+ * ior >= 1, so entry never reflects totally; k2 == ci^2 in exact arithmetic, so the clamp only
+ * meets rounding.  Whatever lies inside the sphere is ignored along the chord, which is not a
+ * closest-hit query: segment counts stay one per accepted query.  A tangent hit (det == 0) is
+ * unspecified.
+ *
+ * RT_PREC_F64 follows the text operation for operation; RT_PREC_PATH64 has the same fp64 path,
+ * (o', d') included, with fp32 colour; RT_PREC_MIXED is served by the F64 kernels.
+ * RT_ERR_UNSUPPORTED, before any launch, while records are set: RT_PREC_F32, RT_FLAG_SUN,
+ * rt_tile_row_costs.  As for lit frames, RT_OPT_PIXEL_PAIRS is ignored, RT_OPT_FRAME_BATCH
+ * launches one frame at a time and RT_OPT_ROW_FEEDBACK neither samples nor reorders;
+ * RT_OPT_MIRROR_BINS is not applied (a ray that passed through a pane did not reflect off it).
+ * RT_OPT_SUPERSAMPLE, row bands, rt_render_device_interleaved, rt_render_device_frames,
+ * rt_multi_*, rt_set_lights and RT_FLAG_SHADOWS work.  rt_trace_rays* with out == NULL,
+ * rt_occluded*, rt_render_aov*, rt_render_ao* and rt_frame_boxes ignore the records. */
+typedef struct rt_transmission {   /* 16 bytes, one per scene object, rt_set_scene order */
+    double transmission;           /* tau in [0, 1]; 0 = opaque: the reference's reflection step */
+    double ior;                    /* index of refraction, finite, in [1, 4]; read for spheres only */
+} rt_transmission;
+int rt_set_transmission(rt_ctx* ctx, const rt_transmission* recs, int32_t n);
+
 /* ---- tuning ------------------------------------------------------------- */
 enum rt_option {
     RT_OPT_WAVE_CULL_MIN_SPHERES = 1, /* scenes with at least this many spheres use the
@@ -768,6 +825,8 @@ int rt_multi_set_option(rt_multi* m, int32_t option, int64_t value);
 /* rt_set_lights on every local rank's ctx (every process of a multi-process operator calls it
  * with the same lights, as rt_multi_set_scene). */
 int rt_multi_set_lights(rt_multi* m, const rt_light* lights, int32_t n);
+/* rt_set_transmission on every local rank's ctx, likewise. */
+int rt_multi_set_transmission(rt_multi* m, const rt_transmission* recs, int32_t n);
 
 /* Enqueue one frame.  d_frame: on the process holding the root, DEVICE memory on the root's
  * device of height x width pixels of out_format (the root's band is rendered into it in

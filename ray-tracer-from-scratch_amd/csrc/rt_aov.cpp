@@ -50,6 +50,7 @@ rt::KParams primary_params(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int3
     FrameOptions opt = ctx->opt;
     opt.ss_log2 = 0;
     opt.lights = false;
+    opt.glass = false;
     opt.pixel_pairs = false;
     opt.mirror_bins = false;  // the primary boxes only
     const FrameReq rq{0, RT_PREC_F64, 0u, RT_OUT_RGB_F32};

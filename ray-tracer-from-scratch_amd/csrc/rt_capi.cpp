@@ -107,6 +107,15 @@ int staged_finish(rt_ctx* ctx, unsigned long long* counter, uint64_t* value, rt_
 
 using namespace rth;
 
+namespace {
+/* Replaced transmission tables, once nothing in flight can read them (hipFree waits for the
+ * device besides). */
+void free_retired_glass(rt_ctx* ctx) {
+    for (rt::DevGlass* t : ctx->glass_retired) (void)hipFree(t);
+    ctx->glass_retired.clear();
+}
+}  // namespace
+
 extern "C" {
 
 int rt_capi_version(void) { return RT_CAPI_VERSION; }
@@ -232,6 +241,8 @@ int rt_ctx_destroy(rt_ctx* ctx) {
     ctx->inflight.clear();
     frame_table_release(ctx);
     if (ctx->d_scene) (void)hipFree(ctx->d_scene);
+    if (ctx->d_glass) (void)hipFree(ctx->d_glass);
+    free_retired_glass(ctx);
     Staging& g = ctx->stg;
     if (g.d_out) (void)hipFree(g.d_out);
     if (g.d_rays) (void)hipFree(g.d_rays);
@@ -263,6 +274,11 @@ int rt_set_scene(rt_ctx* ctx, const rt_prim* prims, int32_t n) {
         ctx->scene_bytes = sc.total;
     }
     RT_HIP(ctx, hipMemcpy(ctx->d_scene, sc.image(), sc.total, hipMemcpyHostToDevice));
+    // the transmission records belonged to the old scene's objects (nothing is in flight)
+    if (ctx->d_glass) ctx->glass_retired.push_back(ctx->d_glass);
+    ctx->d_glass = nullptr;
+    ctx->opt.glass = false;
+    free_retired_glass(ctx);
     ctx->sc = std::move(sc);
     ctx->have_scene = true;
     ctx->scene_gen++;
@@ -276,6 +292,37 @@ int rt_set_lights(rt_ctx* ctx, const rt_light* lights, int32_t n) {
     const int st = pack_lights(lights, n, ctx->lights);  // (leaves ctx->lights alone on failure)
     if (st != RT_OK) return st;
     ctx->opt.lights = ctx->lights.n > 0;
+    return RT_OK;
+}
+
+/* The records go to a device table of their own per set (rt_ctx.h d_glass): no launch in flight
+ * sees another set's records, and nothing is waited for unless many sets pile up. */
+int rt_set_transmission(rt_ctx* ctx, const rt_transmission* recs, int32_t n) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (n > 0 && !ctx->have_scene) return RT_ERR_NO_SCENE;
+    std::vector<rt::DevGlass> tab;
+    const int st = pack_transmission(recs, n, ctx->sc, tab);  // (nothing changes on failure)
+    if (st != RT_OK) return st;
+    DeviceGuard dg(ctx->device);
+    RT_HIP(ctx, dg.err);
+    rt::DevGlass* d_new = nullptr;
+    if (!tab.empty()) {
+        const size_t bytes = tab.size() * sizeof(rt::DevGlass);
+        RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&d_new), bytes));
+        const hipError_t e = hipMemcpy(d_new, tab.data(), bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d_new);
+            return hip_fail(ctx, e, "hipMemcpy(transmission)");
+        }
+    }
+    if (ctx->d_glass) ctx->glass_retired.push_back(ctx->d_glass);
+    ctx->d_glass = d_new;
+    ctx->opt.glass = d_new != nullptr;
+    if (ctx->glass_retired.size() >= 16) {
+        const int ws = wait_inflight(ctx);
+        if (ws != RT_OK) return ws;
+        free_retired_glass(ctx);
+    }
     return RT_OK;
 }
 

@@ -136,6 +136,12 @@ struct rt_ctx {
     unsigned long long scene_gen = 0;  // bumped by every rt_set_scene
     rth::SceneHost sc;
     rt::LightArgs lights{};  // rt_set_lights: n == 0 = the reference's light (plain kernels)
+    // rt_set_transmission: the device table of the records in force (null = none: the kernels a
+    // ctx without records launches).  A set allocates a new table, so launches in flight keep
+    // reading theirs; replaced tables wait in glass_retired until nothing can read them
+    // (wait_inflight: rt_set_scene, rt_ctx_destroy, or a full list).
+    rt::DevGlass* d_glass = nullptr;
+    std::vector<rt::DevGlass*> glass_retired;
     rth::FrameOptions opt;
     rth::BoxCache box_cache;
     rth::BoxCache aov_box_cache;  // rt_render_aov* / rt_render_ao*'s own (rt_aov.cpp primary_params):
@@ -227,7 +233,19 @@ int check_render_args(const rt_ctx* ctx, const rt_camera* cam, int32_t row0, int
                       const FrameReq& rq);
 /* RT_FLAG_SHADOWS and scene lights (rt_capi.h): the shadow and lights kernels exist for the
  * fp64-path precisions without the sun term; checked before anything is launched.  lights: the
- * ctx has lights set (rt_set_lights). */
+ * ctx has lights (rt_set_lights) or transmission records (rt_set_transmission) set. */
+/* The ctx launches kernels of its own for every shaded frame or batch: lights or transmission
+ * records are set. */
+inline bool own_kernels(const rt_ctx* ctx) { return ctx->lights.n > 0 || ctx->d_glass != nullptr; }
+/* What the glass kernels take as lights: the ctx's, or the reference's one white light at the
+ * origin, which gives the plain kernels' bits (rt_capi.h "Lights"). */
+inline rt::LightArgs glass_lights(const rt_ctx* ctx) {
+    if (ctx->lights.n > 0) return ctx->lights;
+    rt::LightArgs la{};
+    for (int k = 0; k < 3; k++) la.l[0].col[k] = 1.0, la.l[0].colf[k] = 1.0f;
+    la.n = 1;
+    return la;
+}
 inline int check_shadow_flags(int32_t precision, uint32_t flags, bool lights = false) {
     if (!(flags & RT_FLAG_SHADOWS) && !lights) return RT_OK;
     if (precision == RT_PREC_F32 || (flags & RT_FLAG_SUN)) return RT_ERR_UNSUPPORTED;

@@ -64,6 +64,8 @@ enum { FLAG_SUN = 1, FLAG_SHADOWS = 2 };
 // Host-internal bit of KParams::flags (never an rt_capi.h flag): the frame was prepared with
 // scene lights set (rt_set_lights) and launches the lights kernels.
 constexpr uint32_t FLAG_LIGHTS = 0x80000000u;
+// The same for transmission records (rt_set_transmission): the frame launches the glass kernels.
+constexpr uint32_t FLAG_GLASS = 0x40000000u;
 
 // Pixel tile of one workgroup: RT_WAVES_PER_BLOCK waves (1, 2 or 4), each an 8x8 square.
 // One wave per workgroup measured fastest (tools/ab.py: c5 -15..21%, c3 -7..12%, c2 -2%
@@ -287,6 +289,29 @@ struct LightArgs {
 int launch_trace_lights(const KParams& p, const LightArgs& la, int prec, void* stream, void* done_event);
 int launch_rays_lights(const KParams& p, const RayArgs& ra, const LightArgs& la, int prec, void* stream,
                        void* done_event);
+
+// Transmission (rt_set_transmission): one record per material slot (spheres, then walls, as
+// KParams::mat), in a device table the ctx owns.  The glass kernels (rt_trace_glass.hip,
+// rt_rays_glass.hip) are the lights kernels with another next-ray step at a hit whose tau > 0 (a
+// pane passes the ray on, a sphere refracts it in, along the chord and out) and w in km's place
+// in the unwind.  The table's pointer travels by value behind the light records.
+struct DevGlass {
+    double tau;  // rt_transmission::transmission; 0 = opaque: the reflection step
+    double ior;  // spheres only
+    double w;    // the unwind's weight: tau > 0 ? tau : the material's metallic
+    float wf;    // w rounded to fp32 (PATH64's colour arithmetic)
+    float pad;
+};
+static_assert(sizeof(DevGlass) == 32, "transmission record layout");
+struct GlassArgs {
+    const DevGlass* rec;  // [nS + nW]
+};
+// A frame / a radiance batch while records are set: launch_trace_lights' / launch_rays_lights'
+// conditions; la holds at least one light (the host passes the reference's when none is set).
+int launch_trace_glass(const KParams& p, const LightArgs& la, const GlassArgs& ga, int prec, void* stream,
+                       void* done_event);
+int launch_rays_glass(const KParams& p, const RayArgs& ra, const LightArgs& la, const GlassArgs& ga, int prec,
+                      void* stream, void* done_event);
 
 // Occlusion queries (rt_occluded*, rt_rays.hip k_ray_occluded): is anything on the segment
 // o .. o + d * tmax of each caller ray?  Only the scene and cull fields of KParams are used.

@@ -47,7 +47,7 @@ int prepare_rows(rt_ctx* ctx, hipStream_t st, rt::KParams& p) {
             p.row_perm_n = gy;
             std::memcpy(p.row_perm, rf.row_perm.data(), gy * sizeof(int16_t));
         }
-    } else if (rf.feedback > 0 && !p.ss_log2 && !(p.flags & (rt::FLAG_SHADOWS | rt::FLAG_LIGHTS)) && rf.fb_band == band &&
+    } else if (rf.feedback > 0 && !p.ss_log2 && !(p.flags & (rt::FLAG_SHADOWS | rt::FLAG_LIGHTS | rt::FLAG_GLASS)) && rf.fb_band == band &&
                !rf.fb.perm.empty()) {
         const int nu = gy << rf.fb_units_log2;
         const bool mix = ctx->row_mix == 2 || (ctx->row_mix == 1 && ctx->frames_overlap && !ctx->last_of_call);
@@ -62,8 +62,9 @@ int prepare_rows(rt_ctx* ctx, hipStream_t st, rt::KParams& p) {
     p.tile_cost = nullptr;
     if (rf.feedback <= 0 || !rf.row_perm.empty() || gy > rt::ROW_PERM_MAX || rf.cost_pending)
         return RT_OK;
-    // supersampled, shadowed and lit (rt_set_lights) frames are never sampled (no stamped kernels)
-    if (p.ss_log2 || (p.flags & (rt::FLAG_SHADOWS | rt::FLAG_LIGHTS))) return RT_OK;
+    // supersampled, shadowed, lit (rt_set_lights) and transmissive (rt_set_transmission) frames
+    // are never sampled (no stamped kernels)
+    if (p.ss_log2 || (p.flags & (rt::FLAG_SHADOWS | rt::FLAG_LIGHTS | rt::FLAG_GLASS))) return RT_OK;
     if (!(rf.fb_band == band)) {
         rf.warm_left = rf.fb_warm;  // a new band or scene: the first snapshot, then the warm ones
     } else if (rf.warm_left > 0) {
@@ -170,6 +171,7 @@ extern "C" int rt_tile_row_costs(rt_ctx* ctx, const rt_camera* cam, int32_t dept
     if (st != RT_OK) return st;
     if (flags & RT_FLAG_SHADOWS) return RT_ERR_UNSUPPORTED;  // no stamped shadow kernels
     if (ctx && ctx->lights.n > 0) return RT_ERR_UNSUPPORTED;  // nor stamped lights kernels
+    if (ctx && ctx->d_glass) return RT_ERR_UNSUPPORTED;       // nor stamped glass kernels
     const int gy = (H + rt::TILE_H - 1) / rt::TILE_H;
     if (!costs || n != gy) return RT_ERR_INVALID_ARG;
     if (gy == 0 || cam->width == 0) {

@@ -388,7 +388,8 @@ rt::KParams make_params(const FrameScene& fs, BoxCache* bc, const rt_camera* cam
     p.nrows = nrows;
     p.depth = rq.depth;
     // (the host-internal bit is never the caller's: other flag bits stay ignored)
-    p.flags = (rq.flags & ~rt::FLAG_LIGHTS) | (opt.lights ? rt::FLAG_LIGHTS : 0u);
+    p.flags = (rq.flags & ~(rt::FLAG_LIGHTS | rt::FLAG_GLASS)) | (opt.lights ? rt::FLAG_LIGHTS : 0u) |
+              (opt.glass ? rt::FLAG_GLASS : 0u);
     p.outf = rq.out_format;
     for (int k = 0; k < 3; k++) {
         p.pos[k] = cam->position[k];
@@ -399,7 +400,7 @@ rt::KParams make_params(const FrameScene& fs, BoxCache* bc, const rt_camera* cam
     p.out = d_out;
     p.segs = d_segs;
     // (one sample per lane when resolving; no two-pixel shadow kernels)
-    p.pairs = (opt.pixel_pairs && !opt.ss_log2 && !(rq.flags & RT_FLAG_SHADOWS) && !opt.lights) ? 1 : 0;
+    p.pairs = (opt.pixel_pairs && !opt.ss_log2 && !(rq.flags & RT_FLAG_SHADOWS) && !opt.lights && !opt.glass) ? 1 : 0;
     p.stats = opt.d_stats;
     // eye tables (rt_device.h) for the linear-scan kernels: the same fp64 operations, in
     // the same order, as sphere_exact / wall_exact on a ray starting at cam->position
@@ -448,7 +449,10 @@ rt::KParams make_params(const FrameScene& fs, BoxCache* bc, const rt_camera* cam
         p.wall_order_n = sc.nW;
     }
     // per-frame boxes, or the previous render's when its inputs were the same
-    const int32_t opts = (opt.tile_bins ? 1 : 0) | (opt.row_order ? 2 : 0) | (opt.mirror_bins ? 4 : 0);
+    // (transmission records: no mirror chains — a ray that passed a pane did not reflect off it)
+    FrameOptions bopt = opt;
+    if (opt.glass) bopt.mirror_bins = false;
+    const int32_t opts = (bopt.tile_bins ? 1 : 0) | (bopt.row_order ? 2 : 0) | (bopt.mirror_bins ? 4 : 0);
     if (bc && opt.box_cache_on && bc->valid && bc->scene_gen == fs.scene_gen && bc->row0 == row0 &&
         bc->nrows == nrows && bc->wave_cull == p.wave_cull && bc->opts == opts &&
         std::memcmp(&bc->cam, cam, sizeof(rt_camera)) == 0) {
@@ -460,7 +464,7 @@ rt::KParams make_params(const FrameScene& fs, BoxCache* bc, const rt_camera* cam
         std::memcpy(p.mbox, bc->mbox, bc->nmbox * sizeof(rt::PrimBox));
         return p;
     }
-    frame_boxes(sc, opt, cam, row0, nrows, p);
+    frame_boxes(sc, bopt, cam, row0, nrows, p);
     if (!bc) return p;
     long nm = 0;
     for (long L = 1, lvl = 1; L <= p.mir_depth; L++) {

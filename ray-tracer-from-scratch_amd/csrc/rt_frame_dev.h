@@ -3,8 +3,8 @@
  * lane (trace_pair_p64) and in fp32 (trace_pixel_f), band rows, the supersample resolve, a
  * wave's tile, a workgroup of the grid and the frame kernel k_trace.  Not a header of its own:
  * included inside the namespace of a frame unit (rt_trace.hip, rt_trace_stamp.hip,
- * rt_trace_shadow.hip, rt_trace_lights.hip) behind rt_scan_dev.h; the ray units do not include
- * it. */
+ * rt_trace_shadow.hip, rt_trace_lights.hip, rt_trace_glass.hip) behind rt_scan_dev.h; the ray
+ * units do not include it. */
 
 /* Dispatch order of tile rows (workgroup row blockIdx.y -> tile row).  Per-tile cost is
  * very uneven (sky/ground tiles end after one segment, tiles over reflective walls bounce
@@ -241,7 +241,9 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
         // reflected off one wall (both wave-uniform)
         uint64_t km = ~0ull;
         if (!CULL && k == 0 && p.nbox > 0) km = keep;
+#if !RT_GLASS  // (a ray that passed through a pane did not reflect off it: no mirrored camera)
         if (!CULL && k >= 1 && k <= p.mir_depth) km = mirror_keep<MAXD>(p, alive, st_m, k, tile);
+#endif
         if (CULL && RT_CULL_WALL_BINS && k == 0) km = keep;  // ~0 when the walls have no boxes
         if (LAZY && !terms && (km & smask) != 0) {  // a sphere may be tested
             ray_terms(r);
@@ -375,6 +377,20 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
         push(k, s, ks, h.slot);
 #endif
         n = k + 1;
+#if RT_GLASS
+        // rt_set_transmission: a transmissive hit goes on with the ray that passes through
+        const DevGlass& gl = p.glass.rec[h.slot];
+        if (gl.tau > 0) {
+            const NextRay nr = glass_next(p, gl, r, h, pos, N, nv, nn);
+            if (LAZY) {
+                r = make_ray_lazy(nr.o, nr.d);
+                terms = false;
+            } else {
+                r = make_ray(nr.o, nr.d);
+            }
+            return;
+        }
+#endif
         // start + reflect(d, N) (main.cpp:111-113, vec.cpp:51-57)
         const double cc = 2 * dot(nv, nn);
         if (LAZY) {
@@ -432,11 +448,19 @@ __device__ __forceinline__ d3 trace_pixel_d(const KParams& p, int x, int i, bool
 #if RT_LIGHTS
             if constexpr (COLOR64) {
                 const d3 L = mul3(m.color, D3(ld_l(0, q), ld_l(1, q), ld_l(2, q)));
+#if RT_GLASS
+                c64 = lerp(L, c64, p.glass.rec[mq].w);  // tau in metallic's place where tau > 0
+#else
                 c64 = lerp(L, c64, m.km);  // vec.cpp:45-49 via main.cpp:117
+#endif
             } else {
                 const DevMat32& m32 = p.mat32[mq];
                 const f3 L = mul3(m32.color, F3(ld_l(0, q), ld_l(1, q), ld_l(2, q)));
+#if RT_GLASS
+                const float km = p.glass.rec[mq].wf;
+#else
                 const float km = m32.km;
+#endif
                 c32 = F3(fmaf(km, c32.x - L.x, L.x), fmaf(km, c32.y - L.y, L.y),
                          fmaf(km, c32.z - L.z, L.z));
             }

@@ -79,6 +79,13 @@ int pack_scene(const rt_prim* prims, int32_t n, SceneHost& sc);
  * component. */
 int pack_lights(const rt_light* lights, int32_t n, rt::LightArgs& out);
 
+/* rt_set_transmission's host half: the checked records of scene sc as the glass kernels'
+ * table, one rt::DevGlass per material slot (spheres, then walls; w = tau where tau > 0, else
+ * the slot's metallic).  n == 0 or every transmission exactly 0 gives an empty out: no records.
+ * RT_ERR_INVALID_ARG, with out untouched, for n neither 0 nor sc.nP, null recs with n > 0, a
+ * non-finite field, transmission outside [0, 1] or ior outside [1, 4]. */
+int pack_transmission(const rt_transmission* recs, int32_t n, SceneHost& sc, std::vector<rt::DevGlass>& out);
+
 /* ---- rt_frame_args.cpp ---------------------------------------------------------------- */
 
 /* The options a frame's arguments depend on.  Written by rt_set_option between calls;
@@ -95,6 +102,7 @@ struct FrameOptions {
     bool box_cache_on = true;  // RT_OPT_BOX_CACHE
     int ss_log2 = 0;         // RT_OPT_SUPERSAMPLE: S = 2^ss_log2 rays per pixel side
     bool lights = false;     // rt_set_lights with n > 0: frames carry rt::FLAG_LIGHTS
+    bool glass = false;      // rt_set_transmission with records: frames carry rt::FLAG_GLASS
     unsigned long long* d_stats = nullptr;  // RT_OPT_STATS_DEVICE_PTR (passed on, never read)
 };
 

@@ -1,6 +1,6 @@
 /* rt_knobs.h — what every kernel unit (rt_trace*.hip, rt_rays*.hip) starts with: the system
  * headers, rt_device.h, and the build knobs of the device code with their defaults.  A unit
- * defines RT_STAMP, RT_SHADOW or RT_LIGHTS before it where it wants those kernels.  Knobs that belong to
+ * defines RT_STAMP, RT_SHADOW, RT_LIGHTS or RT_GLASS before it where it wants those kernels.  Knobs that belong to
  * one function stand next to it in rt_scan_dev.h / rt_frame_dev.h. */
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -84,6 +84,12 @@
 #ifndef RT_SHADOW
 #define RT_SHADOW 0 // 1 in rt_trace_shadow.hip (namespace rt::ksh) and rt_rays_shadow.hip (rt::krs):
 #endif              // RT_FLAG_SHADOWS' kernels, a ray to the light at every hit (light_blocked)
+#ifndef RT_GLASS
+#define RT_GLASS 0  // 1 in rt_trace_glass.hip (namespace rt::kgl) and rt_rays_glass.hip (rt::krg):
+#endif              // rt_set_transmission's kernels, the lights kernels with the passage step
+#if RT_GLASS && !defined(RT_LIGHTS)
+#define RT_LIGHTS 1
+#endif
 #ifndef RT_LIGHTS
 #define RT_LIGHTS 0 // 1 in rt_trace_lights.hip (namespace rt::klt) and rt_rays_lights.hip (rt::krl):
 #endif              // rt_set_lights' kernels, a loop over the scene lights at every hit

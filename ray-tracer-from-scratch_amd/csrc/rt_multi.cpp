@@ -1822,6 +1822,15 @@ int rt_multi_set_lights(rt_multi* m, const rt_light* lights, int32_t n) {
     return RT_OK;
 }
 
+int rt_multi_set_transmission(rt_multi* m, const rt_transmission* recs, int32_t n) {
+    if (!m) return RT_ERR_INVALID_ARG;
+    for (Rank* k : m->r) {
+        const int st = rt_set_transmission(k->ctx, recs, n);
+        if (st != RT_OK) return ctx_err(m, k, st, "rt_set_transmission");
+    }
+    return RT_OK;
+}
+
 int rt_multi_set_option(rt_multi* m, int32_t option, int64_t value) {
     if (!m) return RT_ERR_INVALID_ARG;
     if (option == RT_OPT_SUPERSAMPLE) {

@@ -55,10 +55,14 @@ int launch_ray_batch(rt_ctx* ctx, const double* d_origins, const double* d_direc
     ra.shade = d_out ? 1 : 0;
     // RT_FLAG_SHADOWS: the shadow kernels (rt_rays_shadow.hip) shade; scene lights: the lights
     // kernels (rt_rays_lights.hip), with or without the flag; a hits-only call ignores both
+    // transmission records: the glass kernels (rt_rays_glass.hip), lights or not
+    const bool glass = d_out && ctx->d_glass;
     const bool lights = d_out && ctx->lights.n > 0;
     const bool shadows = d_out && (rq.flags & RT_FLAG_SHADOWS);
-    if ((shadows || lights) && (rq.flags & RT_FLAG_SUN)) return RT_ERR_UNSUPPORTED;
-    const int e = lights    ? rt::launch_rays_lights(p, ra, ctx->lights, prec, hs, done)
+    if ((shadows || lights || glass) && (rq.flags & RT_FLAG_SUN)) return RT_ERR_UNSUPPORTED;
+    const int e = glass     ? rt::launch_rays_glass(p, ra, glass_lights(ctx), rt::GlassArgs{ctx->d_glass}, prec, hs,
+                                                    done)
+                  : lights  ? rt::launch_rays_lights(p, ra, ctx->lights, prec, hs, done)
                   : shadows ? rt::launch_rays_shadow(p, ra, prec, hs, done)
                             : rt::launch_rays(p, ra, prec, hs, done);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "launch k_rays");
@@ -129,7 +133,7 @@ int rt_trace_rays(rt_ctx* ctx, const double* origins, const double* directions, 
                   rt_hit* hits, int32_t count_segments, rt_stats* stats) {
     const FrameReq rq{depth, precision, flags, out_format};
     int st = check_ray_args(ctx, origins, directions, n, rq, out, hits);
-    if (st == RT_OK && out) st = check_shadow_flags(precision, flags, ctx->lights.n > 0);
+    if (st == RT_OK && out) st = check_shadow_flags(precision, flags, own_kernels(ctx));
     if (st != RT_OK) return st;
     if (n == 0) return no_rays(stats);
     DeviceGuard dg(ctx->device);

@@ -13,7 +13,8 @@
  *
  * Not a header of its own: included inside the namespace of a ray unit (rt_rays.hip, rt::kry;
  * rt_rays_shadow.hip, rt::krs, with the light ray of RT_FLAG_SHADOWS; rt_rays_lights.hip,
- * rt::krl, with the scene lights of rt_set_lights) behind rt_scan_dev.h. */
+ * rt::krl, with the scene lights of rt_set_lights; rt_rays_glass.hip, rt::krg, with the
+ * passage step of rt_set_transmission) behind rt_scan_dev.h. */
 #ifndef RT_RAY_STACK_LDS
 #define RT_RAY_STACK_LDS 1
 #endif
@@ -224,6 +225,15 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
         push(k, s, ks, h.slot);
 #endif
         n = k + 1;
+#if RT_GLASS
+        // rt_set_transmission: a transmissive hit goes on with the ray that passes through
+        const DevGlass& gl = p.glass.rec[h.slot];
+        if (gl.tau > 0) {
+            const NextRay nr = glass_next(p, gl, r, h, pos, N, nv, nn);
+            r = make_ray(nr.o, nr.d);
+            return;
+        }
+#endif
         // start + reflect(d, N) (main.cpp:111-113, vec.cpp:51-57)
         const double cc = 2 * dot(nv, nn);
         r = make_ray(pos + N * .0001, nv - nn * cc);
@@ -246,11 +256,19 @@ __device__ __forceinline__ d3 trace_ray_d(const KParams& p, const RayArgs& ra, s
 #if RT_LIGHTS
             if constexpr (COLOR64) {
                 const d3 L = mul3(m.color, D3(ld_l(0, q), ld_l(1, q), ld_l(2, q)));
+#if RT_GLASS
+                c64 = lerp(L, c64, p.glass.rec[mq].w);  // tau in metallic's place where tau > 0
+#else
                 c64 = lerp(L, c64, m.km);  // vec.cpp:45-49 via main.cpp:117
+#endif
             } else {
                 const DevMat32& m32 = p.mat32[mq];
                 const f3 L = mul3(m32.color, F3(ld_l(0, q), ld_l(1, q), ld_l(2, q)));
+#if RT_GLASS
+                const float km = p.glass.rec[mq].wf;
+#else
                 const float km = m32.km;
+#endif
                 c32 = F3(fmaf(km, c32.x - L.x, L.x), fmaf(km, c32.y - L.y, L.y),
                          fmaf(km, c32.z - L.z, L.z));
             }

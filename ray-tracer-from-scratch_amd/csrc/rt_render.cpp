@@ -109,6 +109,11 @@ void prep_main(rt_ctx* ctx) {
  * shadow kernels (rt_trace_shadow.hip) for a flagged frame without lights. */
 int launch_frame(const rt_ctx* ctx, const rt::KParams& p, int32_t precision, void* stream,
                  void* done_event = nullptr) {
+    if (p.flags & rt::FLAG_GLASS) {  // rt_set_transmission: the glass kernels, lights or not
+        if (!ctx->d_glass) return (int)hipErrorInvalidValue;
+        return rt::launch_trace_glass(p, glass_lights(ctx), rt::GlassArgs{ctx->d_glass}, precision, stream,
+                                      done_event);
+    }
     if (p.flags & rt::FLAG_LIGHTS)
         return rt::launch_trace_lights(p, ctx->lights, precision, stream, done_event);
     if (p.flags & rt::FLAG_SHADOWS) return rt::launch_trace_shadow(p, precision, stream, done_event);
@@ -162,7 +167,7 @@ int render_device_impl(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t 
 #endif
     HP_START();
     int st = check_render_args(ctx, cam, row0, nrows, rq);
-    if (st == RT_OK) st = check_shadow_flags(rq.precision, rq.flags, ctx->lights.n > 0);
+    if (st == RT_OK) st = check_shadow_flags(rq.precision, rq.flags, own_kernels(ctx));
     if (st != RT_OK) return st;
     if (!d_out && nrows > 0 && cam->width > 0) return RT_ERR_INVALID_ARG;
     if (ctx->opt.ss_log2 && il) return RT_ERR_UNSUPPORTED;  // contiguous bands only
@@ -267,10 +272,10 @@ int launch_frame_groups(rt_ctx* ctx, const FrameBatch& b, const FrameReq& rq) {
             if (st != RT_OK) break;
             const bool other_grid = n > 0 && (p.W != grp[0].W || p.nrows != grp[0].nrows ||
                                               p.row_units_log2 != grp[0].row_units_log2);
-            // (no table kernels for the cull, pair, supersample, shadow and lights paths: one
+            // (no table kernels for the cull, pair, supersample, shadow, lights and glass paths: one
             // launch each)
             if (p.tile_cost || other_grid || p.wave_cull || p.pairs || p.ss_log2 ||
-                (p.flags & (rt::FLAG_SHADOWS | rt::FLAG_LIGHTS))) {
+                (p.flags & (rt::FLAG_SHADOWS | rt::FLAG_LIGHTS | rt::FLAG_GLASS))) {
                 // this frame alone (after the frames grouped so far), through the per-frame path
                 const rt::KParams one = p;
                 st = launch_group(ctx, s, n, rq.precision, hs);
@@ -421,7 +426,7 @@ int rt_render_device_frames(rt_ctx* ctx, const rt_camera* cams, int32_t ncams, i
     if (!ctx || !cams || ncams <= 0 || !d_outs || nouts <= 0 || nframes < 0 ||
         (nstreams > 0 && !streams) || nstreams < 0)
         return RT_ERR_INVALID_ARG;
-    if (nframes > 0 && check_shadow_flags(precision, flags, ctx->lights.n > 0) != RT_OK)
+    if (nframes > 0 && check_shadow_flags(precision, flags, own_kernels(ctx)) != RT_OK)
         return RT_ERR_UNSUPPORTED;
     const FrameReq rq{depth, precision, flags, out_format};
     const FrameBatch b{cams, ncams, row0, nrows, d_outs, nouts, streams, nstreams, nframes};
@@ -457,7 +462,7 @@ int rt_render(rt_ctx* ctx, const rt_camera* cam, int32_t row0, int32_t nrows, in
               int32_t count_segments, rt_stats* stats) {
     const FrameReq rq{depth, precision, flags, out_format};
     int st = check_render_args(ctx, cam, row0, nrows, rq);
-    if (st == RT_OK) st = check_shadow_flags(precision, flags, ctx->lights.n > 0);
+    if (st == RT_OK) st = check_shadow_flags(precision, flags, own_kernels(ctx));
     if (st != RT_OK) return st;
     const size_t bytes = (size_t)nrows * (size_t)cam->width * (size_t)bytes_per_pixel(out_format);
     if (!out && bytes > 0) return RT_ERR_INVALID_ARG;

@@ -1283,6 +1283,59 @@ __device__ __forceinline__ d3 mul3(const double* c, d3 v) { return D3(c[0] * v.x
 __device__ __forceinline__ f3 mul3(const float* c, f3 v) { return F3(c[0] * v.x, c[1] * v.y, c[2] * v.z); }
 #endif
 
+#if RT_GLASS
+/* Transmission (rt_set_transmission, rt_capi.h "Transmission").  The glass units rename KParams
+ * to their KParamsG, which carries the table of per-slot records behind the light records
+ * (p.glass.rec).  At a hit whose record has tau > 0 the path goes on with the ray that passes
+ * through the object instead of the reflected one; fp64 in every precision, one IEEE operation
+ * per written operation (this TU: -ffp-contract=off; sqrt_e, normalize_e and div_r round
+ * correctly). */
+struct NextRay {
+    d3 o, d;
+};
+/* A wall is a thin pane: the ray goes on unbent from just behind the side it came to.  pos:
+ * main.cpp:99's point, n: the stored normal. */
+__device__ __forceinline__ NextRay glass_pane(const d3 pos, const d3 n, const d3 d) {
+    const double f = dot(d, n);
+    const d3 nf = f > 0 ? -n : n;
+    return {pos - nf * .0001, d};
+}
+/* A sphere of centre c: refract in at P (scene.cpp:75's intersection point), follow the chord to
+ * the far side Q in closed form — Sphere::intersect never reports the far root, and whatever lies
+ * inside the ball is ignored — and refract out.  dh = normalize(d), nh = normalize(P - c).
+ * ior >= 1, so entry never reflects totally; at the exit k2 == ci^2 in exact arithmetic and the
+ * clamp only meets rounding. */
+__device__ __forceinline__ NextRay glass_sphere(const d3 P, const d3 c, const d3 dh, const d3 nh,
+                                                double ior) {
+    const double ci = -dot(dh, nh);
+    const double eta = 1.0 / ior;
+    const double k = 1.0 - (eta * eta) * (1.0 - ci * ci);
+    const d3 t = dh * eta + nh * (eta * ci - sqrt_e(k));
+    const d3 m = c - P;
+    const double s = (2.0 * dot(t, m)) / dot(t, t);
+    const d3 Q = P + t * s;
+    const d3 n2 = Q - c;
+    const d3 n2h = normalize_e(n2);
+    const d3 th = normalize_e(t);
+    const double c2 = dot(th, n2h);
+    const double k2 = 1.0 - (ior * ior) * (1.0 - c2 * c2);
+    const double k2c = k2 > 0 ? k2 : 0.0;
+    return {Q + n2 * .0001, th * ior + n2h * (sqrt_e(k2c) - ior * c2)};
+}
+/* The next ray of a transmissive hit (g.tau > 0) of ray r at slot: P = r.o + r.d * h.pt for a
+ * sphere, pos = r.o + r.d * h.dist for a wall; N the record normal, nv and nn the normalised
+ * direction and normal the shading step formed. */
+__device__ __forceinline__ NextRay glass_next(const KParams& p, const DevGlass& g, const RayD& r,
+                                              const HitD& h, const d3 pos, const d3 N, const d3 nv,
+                                              const d3 nn) {
+    if (h.slot < p.nS) {
+        const double* S = p.s64[h.slot >> 2].v[h.slot & 3];
+        return glass_sphere(r.o + r.d * h.pt, D3(S[0], S[1], S[2]), nv, nn, g.ior);
+    }
+    return glass_pane(pos, N, r.d);
+}
+#endif
+
 /* ------------------------------------------------------------------------ */
 /* epilogue: pixel store, segment count, occupancy targets                   */
 /* ------------------------------------------------------------------------ */

@@ -330,4 +330,33 @@ int pack_lights(const rt_light* lights, int32_t n, rt::LightArgs& out) {
     return RT_OK;
 }
 
+int pack_transmission(const rt_transmission* recs, int32_t n, SceneHost& sc, std::vector<rt::DevGlass>& out) {
+    if ((n != 0 && n != sc.nP) || (n > 0 && !recs)) return RT_ERR_INVALID_ARG;
+    bool any = false;
+    for (int32_t j = 0; j < n; j++) {
+        const double tau = recs[j].transmission, ior = recs[j].ior;
+        if (!std::isfinite(tau) || !std::isfinite(ior)) return RT_ERR_INVALID_ARG;
+        if (tau < 0.0 || tau > 1.0 || ior < 1.0 || ior > 4.0) return RT_ERR_INVALID_ARG;
+        any = any || tau != 0.0;
+    }
+    std::vector<rt::DevGlass> tab;
+    if (any) {
+        // material-slot order: spheres, then walls, each with its scene index (pack_scene)
+        const int32_t* sj = reinterpret_cast<const int32_t*>(sc.image() + sc.off_sj);
+        const int32_t* wj = reinterpret_cast<const int32_t*>(sc.image() + sc.off_wj);
+        tab.resize((size_t)sc.nS + (size_t)sc.nW);
+        for (size_t k = 0; k < tab.size(); k++) {
+            const rt_transmission& r = recs[k < (size_t)sc.nS ? sj[k] : wj[k - (size_t)sc.nS]];
+            rt::DevGlass& g = tab[k];
+            g.tau = r.transmission;
+            g.ior = r.ior;
+            g.w = r.transmission > 0.0 ? r.transmission : sc.h_km[k];
+            g.wf = (float)g.w;
+            g.pad = 0.0f;
+        }
+    }
+    out.swap(tab);
+    return RT_OK;
+}
+
 }  // namespace rth

@@ -17,7 +17,7 @@
  *   rt_frames [--frames N] [--keys wwaassdd] [--width W] [--depth D] [--precision f64|mixed|
  *             path64|f32] [--scene default|synthetic:S,W[,seed]] [--ppm file] [--gpu-surface]
  *             [--supersample 1|2|4|8] [--shadows] [--light x,y,z[,r,g,b]]... [--aov PREFIX]
- *             [--ao PREFIX [--ao-dirs K] [--ao-radius R]]
+ *             [--ao PREFIX [--ao-dirs K] [--ao-radius R]] [--glass INDEX,TAU[,IOR]]...
  *
  * --gpu-surface replaces rt_scene + the host packing loop by one rt_render with the
  * kernel's RT_OUT_RGBA8_WRAP epilogue: the same bytes main.cpp:345 produces, highlights
@@ -29,6 +29,9 @@
  * --light x,y,z[,r,g,b] adds a point light (rt_set_lights; colour 1,1,1 when omitted),
  * repeatable up to RT_MAX_LIGHTS times: the lights given replace the reference's white light at
  * the origin, on either path; not with --precision f32.
+ * --glass INDEX,TAU[,IOR] makes scene object INDEX transmissive (rt_set_transmission: TAU in
+ * [0, 1], IOR in [1, 4], 1.5 when omitted; a wall is a thin pane, a sphere solid glass),
+ * repeatable, on either path; not with --precision f32.
  * --aov PREFIX writes the first frame's G-buffer layers (rt_scene_aov; not in the reference)
  * as raw row-major files: PREFIX.depth.f32 (world distance of the primary hit, +inf = miss) and
  * PREFIX.index.i32 (scene index, -1 = miss), image_height x width values each.
@@ -67,6 +70,11 @@ struct Args {
     int supersample = 1;
     bool shadows = false;
     std::vector<RtLight> lights;
+    struct Glass {
+        int index;
+        double tau, ior;
+    };
+    std::vector<Glass> glass;
     std::string aov;
     std::string ao;
     int ao_dirs = 16;
@@ -116,6 +124,17 @@ Args parse(int argc, char** argv) {
                 std::exit(2);
             }
             a.lights.push_back(RtLight{point3(v[0], v[1], v[2]), RGB(v[3], v[4], v[5])});
+        }
+        else if (o == "--glass") {
+            int idx = -1;
+            double tau = 0, ior = 1.5;
+            const std::string s = val();
+            const int got = std::sscanf(s.c_str(), "%d,%lf,%lf", &idx, &tau, &ior);
+            if ((got != 2 && got != 3) || idx < 0) {
+                std::fprintf(stderr, "--glass takes INDEX,TAU[,IOR]\n");
+                std::exit(2);
+            }
+            a.glass.push_back(Args::Glass{idx, tau, ior});
         }
         else if (o == "--supersample") {
             a.supersample = std::atoi(val().c_str());
@@ -214,6 +233,16 @@ int main(int argc, char** argv) {
     opts.supersample = a.supersample;
     if (a.shadows) opts.flags |= RT_FLAG_SHADOWS;
     opts.lights = a.lights;
+    if (!a.glass.empty()) {
+        opts.transmission.assign(scene.size(), RtTransmission{});
+        for (const Args::Glass& g : a.glass) {
+            if ((size_t)g.index >= scene.size()) {
+                std::fprintf(stderr, "--glass: the scene has %zu objects\n", scene.size());
+                return 2;
+            }
+            opts.transmission[(size_t)g.index] = RtTransmission{g.tau, g.ior};
+        }
+    }
     rt_scene_set_options(opts);
 
     const int W = a.width, H = (int)cam.image_height;
@@ -235,6 +264,12 @@ int main(int argc, char** argv) {
         for (const RtLight& l : a.lights)
             ls.push_back(rt_light{{l.position.x, l.position.y, l.position.z}, {l.color.x, l.color.y, l.color.z}});
         if (rt_set_lights(ctx, ls.data(), (int32_t)ls.size()) != RT_OK) return 1;
+        std::vector<rt_transmission> ts;
+        for (const RtTransmission& t : opts.transmission) ts.push_back(rt_transmission{t.transmission, t.ior});
+        if (rt_set_transmission(ctx, ts.data(), (int32_t)ts.size()) != RT_OK) {
+            std::fprintf(stderr, "rt_set_transmission refused the --glass records\n");
+            return 1;
+        }
     }
 
     std::vector<int64_t> total_times, rt_times, outpainting_times, shading_times,

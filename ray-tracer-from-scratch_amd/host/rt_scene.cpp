@@ -38,6 +38,9 @@ struct Global {
     std::vector<rt_prim> uploaded;  // the scene on the device (re-uploaded only on change)
     bool uploaded_tiled = false;    // ... of the tiled (rt_multi) or the one-GPU renderer
     std::vector<rt_prim> ctx_prims;  // the scene on `ctx` itself (the ray queries always use it)
+    // the transmission records in force on `ctx` / `multi` (set only on change: a set uploads a
+    // table); emptied wherever the renderer or its scene is replaced, which clears the records
+    std::vector<rt_transmission> ctx_glass, multi_glass;
     bool atexit_set = false;
     // no destructor: a function-static's destructor runs in an order unspecified relative
     // to the HIP and RCCL runtimes' own teardown; rt_scene_shutdown (atexit) releases
@@ -51,6 +54,8 @@ struct Global {
         multi_transport = -1;
         uploaded.clear();
         ctx_prims.clear();
+        ctx_glass.clear();
+        multi_glass.clear();
     }
 };
 
@@ -87,6 +92,25 @@ std::vector<rt_light> light_records(const RtSceneOptions& o) {
         ls[l] = rt_light{{s.position.x, s.position.y, s.position.z}, {s.color.x, s.color.y, s.color.z}};
     }
     return ls;
+}
+
+/* RtSceneOptions::transmission in force on the one-GPU renderer (tiled == false) or the
+ * row-tiled one: rt_set_transmission / rt_multi_set_transmission when the records differ from
+ * those set last (an empty vector: none). */
+void apply_transmission(Global& g, bool tiled) {
+    std::vector<rt_transmission> want(g.opts.transmission.size());
+    for (size_t j = 0; j < want.size(); j++)
+        want[j] = rt_transmission{g.opts.transmission[j].transmission, g.opts.transmission[j].ior};
+    std::vector<rt_transmission>& have = tiled ? g.multi_glass : g.ctx_glass;
+    if (want.size() == have.size() &&
+        (want.empty() || std::memcmp(want.data(), have.data(), want.size() * sizeof(rt_transmission)) == 0))
+        return;
+    if (tiled)
+        check_multi(rt_multi_set_transmission(g.multi, want.data(), (int32_t)want.size()), g.multi,
+                    "rt_multi_set_transmission");
+    else
+        check(rt_set_transmission(g.ctx, want.data(), (int32_t)want.size()), g.ctx, "rt_set_transmission");
+    have.swap(want);
 }
 
 /* The frame's camera as the C-ABI takes it: position and image_top_left of cam, the pixel
@@ -153,6 +177,7 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
         g.multi_devices = g.opts.devices;
         g.multi_transport = g.opts.transport;
         g.uploaded.clear();
+        g.multi_glass.clear();
     } else if (!tiled && (!g.ctx || g.ctx_device != g.opts.device)) {
         if (g.ctx) rt_ctx_destroy(g.ctx);
         g.ctx = nullptr;
@@ -160,6 +185,7 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
         g.ctx_device = g.opts.device;
         g.uploaded.clear();
         g.ctx_prims.clear();
+        g.ctx_glass.clear();
     }
     register_shutdown(g);
     if (tiled != g.uploaded_tiled) g.uploaded.clear();
@@ -169,6 +195,7 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
     if (g.uploaded.empty() || prims.size() != g.uploaded.size() ||
         std::memcmp(prims.data(), g.uploaded.data(), prims.size() * sizeof(rt_prim)) != 0) {
         g.uploaded.clear();
+        (tiled ? g.multi_glass : g.ctx_glass).clear();  // rt_set_scene clears the records
         if (tiled)
             check_multi(rt_multi_set_scene(g.multi, prims.data(), (int32_t)prims.size()), g.multi,
                         "rt_multi_set_scene");
@@ -188,6 +215,7 @@ void rt_scene(std::vector<vec3> u, const std::vector<std::unique_ptr<SceneGeomet
                     "rt_multi_set_lights");
     else
         check(rt_set_lights(g.ctx, ls.data(), (int32_t)ls.size()), g.ctx, "rt_set_lights");
+    apply_transmission(g, tiled);
     if (tiled)
         check_multi(rt_multi_render(g.multi, &c, g.opts.depth, g.opts.precision, g.opts.flags,
                                     RT_OUT_RGB_F64, g.staging.data(), nullptr),
@@ -219,6 +247,7 @@ void ray_scene(Global& g, const std::vector<std::unique_ptr<SceneGeometry>>& sce
         if (g.ctx) rt_ctx_destroy(g.ctx);
         g.ctx = nullptr;
         g.ctx_prims.clear();
+        g.ctx_glass.clear();
         if (!g.uploaded_tiled) g.uploaded.clear();
         check(rt_ctx_create(g.opts.device, &g.ctx), nullptr, "rt_ctx_create");
         g.ctx_device = g.opts.device;
@@ -228,6 +257,7 @@ void ray_scene(Global& g, const std::vector<std::unique_ptr<SceneGeometry>>& sce
     if (g.ctx_prims.empty() || prims.size() != g.ctx_prims.size() ||
         std::memcmp(prims.data(), g.ctx_prims.data(), prims.size() * sizeof(rt_prim)) != 0) {
         g.ctx_prims.clear();
+        g.ctx_glass.clear();  // rt_set_scene clears the records
         if (!g.uploaded_tiled) g.uploaded.clear();
         check(rt_set_scene(g.ctx, prims.data(), (int32_t)prims.size()), g.ctx, "rt_set_scene");
         g.ctx_prims = prims;
@@ -370,6 +400,7 @@ std::vector<RGB> rt_radiance(const std::vector<std::unique_ptr<SceneGeometry>>& 
     const int prec = g.opts.precision == RT_PREC_MIXED ? RT_PREC_F64 : g.opts.precision;
     const std::vector<rt_light> ls = light_records(g.opts);
     check(rt_set_lights(g.ctx, ls.data(), (int32_t)ls.size()), g.ctx, "rt_set_lights");
+    apply_transmission(g, false);
     std::vector<double> rgb(rays.size() * 3);
     check(rt_trace_rays(g.ctx, o.data(), d.data(), (int64_t)rays.size(), remaining_iterations, prec,
                         g.opts.flags, RT_OUT_RGB_F64, rgb.data(), nullptr, 0, nullptr),

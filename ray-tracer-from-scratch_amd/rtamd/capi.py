@@ -137,6 +137,25 @@ def light_array(lights):
     return (rt_light * len(recs))(*recs), len(recs)
 
 
+class rt_transmission(C.Structure):
+    """A transmission record of rt_set_transmission (16 bytes), one per scene object."""
+    _fields_ = [("transmission", C.c_double), ("ior", C.c_double)]
+
+
+def transmission_array(recs):
+    """recs as a ctypes array of rt_transmission: rt_transmission records, (tau, ior) pairs, or
+    a plain 0 for an opaque object (ior 1).  None or an empty list gives (None, 0): no records."""
+    out = []
+    for r in recs or []:
+        if not isinstance(r, rt_transmission):
+            tau, ior = (r, 1.0) if isinstance(r, (int, float)) else r
+            r = rt_transmission(tau, ior)
+        out.append(r)
+    if not out:
+        return None, 0
+    return (rt_transmission * len(out))(*out), len(out)
+
+
 class rt_stats(C.Structure):
     _fields_ = [("ms", C.c_double), ("segments", C.c_uint64)]
 
@@ -192,6 +211,7 @@ SIGNATURES = [
     ("rt_capi_version", C.c_int, []),
     ("rt_set_scene", C.c_int, [C.c_void_p, C.POINTER(rt_prim), C.c_int32]),
     ("rt_set_lights", C.c_int, [C.c_void_p, C.POINTER(rt_light), C.c_int32]),
+    ("rt_set_transmission", C.c_int, [C.c_void_p, C.POINTER(rt_transmission), C.c_int32]),
     ("rt_set_option", C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     ("rt_render", C.c_int,
      [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -259,6 +279,7 @@ SIGNATURES = [
     ("rt_multi_set_scene", C.c_int, [C.c_void_p, C.POINTER(rt_prim), C.c_int32]),
     ("rt_multi_set_option", C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     ("rt_multi_set_lights", C.c_int, [C.c_void_p, C.POINTER(rt_light), C.c_int32]),
+    ("rt_multi_set_transmission", C.c_int, [C.c_void_p, C.POINTER(rt_transmission), C.c_int32]),
     ("rt_multi_render_device", C.c_int,
      [C.c_void_p, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p,
       C.c_void_p]),
@@ -476,6 +497,13 @@ class Renderer:
         reference's white light at the origin."""
         arr, n = light_array(lights)
         check(self.lib.rt_set_lights(self.ctx, arr, n), self.ctx)
+
+    def set_transmission(self, recs) -> None:
+        """rt_set_transmission: one (tau, ior) pair (or rt_transmission, or 0 = opaque) per scene
+        object, in set_scene's order, for every launch enqueued afterwards; None or [] clears
+        the records, and so does a list whose every tau is 0."""
+        arr, n = transmission_array(recs)
+        check(self.lib.rt_set_transmission(self.ctx, arr, n), self.ctx)
 
     def set_option(self, option: int, value: int) -> None:
         check(self.lib.rt_set_option(self.ctx, option, value), self.ctx)
@@ -781,6 +809,11 @@ class MultiRenderer:
         """rt_multi_set_lights: Renderer.set_lights on every local rank."""
         arr, n = light_array(lights)
         self._check(self.lib.rt_multi_set_lights(self.m, arr, n))
+
+    def set_transmission(self, recs) -> None:
+        """rt_multi_set_transmission: Renderer.set_transmission on every local rank."""
+        arr, n = transmission_array(recs)
+        self._check(self.lib.rt_multi_set_transmission(self.m, arr, n))
 
     def set_option(self, option: int, value: int) -> None:
         self._check(self.lib.rt_multi_set_option(self.m, option, value))

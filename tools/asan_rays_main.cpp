@@ -4,8 +4,9 @@
 // runtime).  It packs scenes through the host-only rt_frame_boxes (pack_scene: spheres,
 // walls, an interleaved order, a wall with a NaN basis), orders dispatch units through the
 // host-only rt_order_units (rt_row_order.cpp), walks the argument checks of
-// rt_trace_rays, rt_trace_rays_device, rt_occluded*, rt_render_aov* and rt_set_lights, and
-// converts hit records to Collisions.  Where a HIP device exists it also runs the entry points on a small batch; without one
+// rt_trace_rays, rt_trace_rays_device, rt_occluded*, rt_render_aov*, rt_set_lights and
+// rt_set_transmission (its host half, pack_transmission, directly: a set, both ways of clearing
+// and every refused argument, with no device), and converts hit records to Collisions.  Where a HIP device exists it also runs the entry points on a small batch; without one
 // rt_ctx_create returns RT_ERR_NO_DEVICE and the device part is skipped (and said so).
 #include <algorithm>
 #include <cfloat>
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "rt/scene.h"
+#include "../ray-tracer-from-scratch_amd/csrc/rt_host.h"  // pack_scene, pack_transmission (linked in)
 
 static int g_fail = 0;
 #define EXPECT(cond)                                                      \
@@ -125,6 +127,47 @@ int main() {
     EXPECT(rt_set_lights(nullptr, lights, 1) == RT_ERR_INVALID_ARG);
     EXPECT(rt_multi_set_lights(nullptr, lights, 1) == RT_ERR_INVALID_ARG);
     EXPECT(sizeof(rt_light) == 48);
+    // rt_set_transmission: without a ctx; then its host half on the packed scene (45 objects, 44
+    // material slots: the NaN wall has none): a set, the refusals (the table stays), the clears
+    std::vector<rt_transmission> recs(prims.size(), rt_transmission{0.0, 1.0});
+    EXPECT(rt_set_transmission(nullptr, recs.data(), (int32_t)recs.size()) == RT_ERR_INVALID_ARG);
+    EXPECT(rt_multi_set_transmission(nullptr, recs.data(), (int32_t)recs.size()) == RT_ERR_INVALID_ARG);
+    EXPECT(sizeof(rt_transmission) == 16);
+    {
+        const int32_t n = (int32_t)prims.size();
+        rth::SceneHost sc;
+        EXPECT(rth::pack_scene(prims.data(), n, sc) == RT_OK);
+        std::vector<rt::DevGlass> tab;
+        recs[0] = rt_transmission{0.6, 1.0};   // the first wall: slot nS + 0
+        recs[1] = rt_transmission{0.9, 1.5};   // the first sphere: slot 0
+        recs[n - 1] = rt_transmission{1.0, 4.0};
+        EXPECT(rth::pack_transmission(recs.data(), n, sc, tab) == RT_OK);
+        EXPECT(tab.size() == (size_t)(sc.nS + sc.nW) && sc.nS + sc.nW == n - 1);
+        EXPECT(tab[0].tau == 0.9 && tab[0].ior == 1.5 && tab[0].w == 0.9 && tab[0].wf == 0.9f);
+        EXPECT(tab[(size_t)sc.nS].tau == 0.6 && tab[(size_t)sc.nS].w == 0.6);
+        EXPECT(tab[1].tau == 0.0 && tab[1].w == 0.2);   // opaque: the slot's metallic
+        EXPECT(tab[(size_t)sc.nS - 1].tau == 1.0 && tab[(size_t)sc.nS - 1].ior == 4.0);
+        const std::vector<rt::DevGlass> kept = tab;
+        auto refused = [&](const rt_transmission* r, int32_t cnt) {
+            return rth::pack_transmission(r, cnt, sc, tab) == RT_ERR_INVALID_ARG && tab.size() == kept.size() &&
+                   std::memcmp(tab.data(), kept.data(), kept.size() * sizeof(rt::DevGlass)) == 0;
+        };
+        EXPECT(refused(recs.data(), n - 1));
+        EXPECT(refused(recs.data(), n + 1));
+        EXPECT(refused(recs.data(), -1));
+        EXPECT(refused(nullptr, n));
+        const rt_transmission bad[] = {{std::nan(""), 1.5}, {0.5, std::nan("")}, {0.5, INFINITY}, {-0.01, 1.5},
+                                       {1.01, 1.5},         {0.5, 0.99},         {0.5, 4.01},     {0.0, 0.5}};
+        for (const rt_transmission& b : bad) {
+            std::vector<rt_transmission> r2 = recs;
+            r2[7] = b;
+            EXPECT(refused(r2.data(), n));
+        }
+        std::vector<rt_transmission> zeros(prims.size(), rt_transmission{0.0, 2.5});
+        EXPECT(rth::pack_transmission(zeros.data(), n, sc, tab) == RT_OK && tab.empty());
+        tab = kept;
+        EXPECT(rth::pack_transmission(nullptr, 0, sc, tab) == RT_OK && tab.empty());
+    }
     // frame AOVs: what is refused before the ctx is looked at, the buffers untouched
     EXPECT(sizeof(rt_aov_buffers) == 48);
     int32_t aov_index[2] = {7, 7};
@@ -194,6 +237,22 @@ int main() {
             EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, RT_FLAG_SUN, RT_OUT_RGB_F64, rgb, hits, 1,
                                  &st) == RT_ERR_UNSUPPORTED);
             EXPECT(rt_set_lights(ctx, nullptr, 0) == RT_OK);
+            // rt_set_transmission on the ctx: set, shade, the refusals, clear (both ways)
+            EXPECT(rt_set_transmission(ctx, recs.data(), (int32_t)recs.size()) == RT_OK);
+            EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, RT_FLAG_SHADOWS, RT_OUT_RGB_F64, rgb, hits, 1,
+                                 &st) == RT_OK);
+            EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, RT_FLAG_SUN, RT_OUT_RGB_F64, rgb, hits, 1,
+                                 &st) == RT_ERR_UNSUPPORTED);
+            EXPECT(rt_set_transmission(ctx, recs.data(), (int32_t)recs.size() - 1) == RT_ERR_INVALID_ARG);
+            EXPECT(rt_set_transmission(ctx, nullptr, (int32_t)recs.size()) == RT_ERR_INVALID_ARG);
+            {
+                const std::vector<rt_transmission> zeros(recs.size(), rt_transmission{0.0, 1.0});
+                EXPECT(rt_set_transmission(ctx, zeros.data(), (int32_t)zeros.size()) == RT_OK);
+            }
+            EXPECT(rt_trace_rays(ctx, o, d, 2, 4, RT_PREC_F64, RT_FLAG_SUN, RT_OUT_RGB_F64, rgb, hits, 1,
+                                 &st) == RT_OK);
+            EXPECT(rt_set_transmission(ctx, recs.data(), (int32_t)recs.size()) == RT_OK);
+            EXPECT(rt_set_transmission(ctx, nullptr, 0) == RT_OK);
             // rt_render_aov: the refused arguments (statuses before any launch), then one row
             const rt_aov_buffers none{};
             rt_aov_buffers bad = ab;
